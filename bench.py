@@ -19,6 +19,10 @@ sampling (weak scaling: 4096 chains per GPU, RNG stream = global chain index); t
 The CPU baseline is the repository's C restatement of the reference path (oracle/, "port") with its tuned density evaluation, run
 on the host cores on a bounded sample of the same two rounds; it is a reported baseline, never the measured path.  The side
 blocks (tools/benchlib/blocks.py) are never part of `value`.
+
+--dump-outputs DIR writes what the last of the K timed launches returned (rank 0's samples and stats, float64; a fixed draw of
+the chains when all of them would pass the size cap) to DIR/<name>.npy.  The inputs are fixed by --seed, so two builds run
+with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -70,6 +74,24 @@ def _dominant_roofline(rounds):
     return rf
 
 
+DUMP_BYTES = 48 << 20   # cap of --dump-outputs (all files together)
+
+
+def _dump_outputs(out_dir, samples, stats, seed):
+    """--dump-outputs: the (samples (C, iters, d), stats (C, iters, 11)) of the line's last timed launch, as float64 .npy files.  Chains
+    beyond the size cap are left out: the ones kept are a sorted draw fixed by --seed (chain_index.npy), the same on every run."""
+    import torch
+    C = samples.shape[0]
+    per_chain = (samples[0].numel() + stats[0].numel() + 1) * 8
+    n = min(C, max(1, DUMP_BYTES // per_chain))
+    idx = np.arange(C) if n == C else np.sort(np.random.default_rng(seed).choice(C, n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    sel = torch.as_tensor(idx, device=samples.device)
+    for name, arr in (('samples', samples.index_select(0, sel).cpu().numpy()), ('stats', stats.index_select(0, sel).cpu().numpy()),
+                      ('chain_index', idx.astype(np.float64))):
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(arr, dtype=np.float64))
+
+
 def main():
     if len(sys.argv) == 3 and sys.argv[1] == '--cpu-child':
         from benchlib import cpu
@@ -89,11 +111,15 @@ def main():
     ap.add_argument('--no-configs', action='store_true', help="skip the blocks on the other BASELINE configs' targets (config2/4/5, DES pipeline, evidence)")
     ap.add_argument('--workload', default=None, choices=blocks.CONFIG_BLOCKS + ('evidence128', 'gauss64'),
                     help='run ONE block only and print it (profiling: rocprofv3 -- python3 bench.py --workload funnel)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed launch returned (samples, stats; a fixed sample of the chains) as DIR/<name>.npy')
     a = ap.parse_args()
     if a.no_extras:
         a.no_configs = True
     if a.gpus < 1:
         ap.error('--gpus should be a positive int')
+    if a.steps < 1:
+        ap.error('--steps should be a positive int')
     if 'WORLD_SIZE' not in os.environ and a.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, BEFORE anything here touches the GPU
         # (fresh children through torch.distributed.run; this process only relays their output and exit code)
@@ -160,6 +186,10 @@ def main():
             timed_rounds = rounds[:1]
         else:
             timed_rounds = rounds
+        outputs = c3.pop('outputs')
+        if a.dump_outputs and rank == 0:
+            _dump_outputs(a.dump_outputs, *outputs[len(timed_rounds) - 1], a.seed)
+        del outputs   # (the device buffers are not kept through the side blocks)
         # max over ranks of each round's bracketed time, sum over ranks of its leapfrogs
         SUM, MAX = (dist.ReduceOp.SUM, dist.ReduceOp.MAX) if dist is not None else (None, None)
         lf_tot = [reduce(r['leapfrogs_timed'], SUM) for r in timed_rounds]

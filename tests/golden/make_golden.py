@@ -1,20 +1,17 @@
 #!/usr/bin/env python3
 """Generate the golden fixtures under tests/golden/ by IMPORTING the reference (h3jia/bayesfast).
 
-Runs only in the build container, where /root/reference exists.  It copies the reference package to a
-scratch directory, builds its four Cython extensions with a plain setuptools script, installs two
-environment shims (removed NumPy aliases; a stub numdifftools) and then records inputs/outputs of the
-reference's own functions on the hot path.  Nothing of the reference's source enters this repository:
+Runs only where a checkout of the reference exists.  Through oracle/reference.py it copies the reference
+package to a scratch directory, builds its four Cython extensions with a plain setuptools script,
+installs two environment shims (removed NumPy aliases; a stub numdifftools) and then records
+inputs/outputs of the reference's own functions on the hot path.  Nothing of the reference's source enters this repository:
 the .npz files hold data only (inputs, coefficients the reference fitted, outputs, logged random draws).
 
 Usage:  python tests/golden/make_golden.py [--ref /root/reference] [--work /tmp/bfref]
 """
 import argparse
 import os
-import shutil
-import subprocess
 import sys
-import types
 
 import numpy as np
 
@@ -22,71 +19,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 from specio import flatten_spec, flatten_poly  # noqa: E402
 
-BUILD_EXT = r'''
-import numpy as np
-from setuptools import setup, Extension
-from Cython.Build import cythonize
-names = ['bayesfast/modules/_poly', 'bayesfast/transforms/_constraint', 'bayesfast/utils/_sobol',
-         'bayesfast/utils/_cubic']
-exts = [Extension(n.replace('/', '.'), [n + '.pyx'], include_dirs=[np.get_include()],
-                  extra_compile_args=['-fopenmp', '-O3'], extra_link_args=['-fopenmp']) for n in names]
-setup(ext_modules=cythonize(exts, language_level='3'))
-'''
-
 
 def prepare_reference(ref, work):
-    pkg = os.path.join(work, 'bayesfast')
-    if not os.path.exists(os.path.join(pkg, 'modules')) or not any(
-            f.endswith('.so') for f in os.listdir(os.path.join(pkg, 'modules'))):
-        os.makedirs(work, exist_ok=True)
-        if os.path.exists(pkg):
-            shutil.rmtree(pkg)
-        shutil.copytree(os.path.join(ref, 'bayesfast'), pkg)
-        with open(os.path.join(work, 'build_ext.py'), 'w') as f:
-            f.write(BUILD_EXT)
-        subprocess.check_call([sys.executable, 'build_ext.py', 'build_ext', '--inplace'], cwd=work,
-                              stdout=subprocess.DEVNULL)
-    # shim 1: NumPy aliases removed in 1.24 that the reference still uses
-    for n, t in (('int', int), ('float', float)):
-        if not hasattr(np, n):
-            setattr(np, n, t)
-    # shim 2: numdifftools is not installed; only Laplace (OptimizeStep) and the reference's tests use it
-    nd = types.ModuleType('numdifftools')
-
-    def _central(f, x, h=1e-6):
-        x = np.atleast_1d(np.asarray(x, dtype=float))
-        f0 = np.atleast_1d(f(x))
-        J = np.empty((f0.size, x.size))
-        for i in range(x.size):
-            e = np.zeros_like(x)
-            e[i] = h
-            J[:, i] = (np.atleast_1d(f(x + e)) - np.atleast_1d(f(x - e))) / (2 * h)
-        return J
-
-    class Gradient:
-        def __init__(self, f, *a, **k):
-            self.f = f
-
-        def __call__(self, x):
-            return _central(self.f, x)[0]
-
-    class Jacobian(Gradient):
-        def __call__(self, x):
-            return _central(self.f, x)
-
-    class Hessian(Gradient):
-        def __call__(self, x):
-            return _central(lambda y: _central(self.f, y)[0], x, 1e-4)
-
-    class Hessdiag(Gradient):
-        def __call__(self, x):
-            return np.diag(Hessian(self.f)(x))
-
-    nd.Gradient, nd.Jacobian, nd.Hessian, nd.Hessdiag = Gradient, Jacobian, Hessian, Hessdiag
-    sys.modules['numdifftools'] = nd
-    sys.path.insert(0, work)
-    import bayesfast  # noqa: F401
-    return bayesfast
+    """The reference built in ``work`` from the checkout ``ref`` (oracle/reference.py: copy, cythonize, two shims), imported."""
+    from oracle import reference
+    if not reference.build(ref, work):
+        raise FileNotFoundError('no reference checkout at %s' % ref)
+    return reference.load(work)
 
 
 # ---------------------------------------------------------------------------------------------------

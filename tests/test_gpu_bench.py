@@ -48,6 +48,23 @@ def test_bench_single_gpu_line():
     assert j['gauss64_best_case']['value'] > 0
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the samples and stats of the line's last timed launch (round 1's with --steps 2), float64, every chain
+    when they fit the size cap; their trees are the leapfrogs the line counts for that launch."""
+    out = tmp_path / 'dump'
+    r = subprocess.run([sys.executable, 'bench.py', '--steps', '2', '--warmup', '1', '--chains', '256', '--no-cpu-baseline', '--no-extras',
+                        '--dump-outputs', str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = _line(r.stdout)
+    import numpy as np
+    s, st, idx = (np.load(out / (n + '.npy')) for n in ('samples', 'stats', 'chain_index'))
+    assert s.dtype == st.dtype == idx.dtype == np.float64
+    assert s.shape == (256, 100, 64) and st.shape == (256, 100, 11) and np.array_equal(idx, np.arange(256.))
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+    assert np.isfinite(s).all()
+    assert st[:, :, 3].sum() == j['config3_round1']['leapfrogs_timed']   # (column 3: tree_size)
+
+
 def test_bench_two_ranks_on_one_gpu_gloo():
     port = 29700 + os.getpid() % 200
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
@@ -65,18 +82,19 @@ def test_bench_two_ranks_on_one_gpu_gloo():
     assert j['layout_vote']['ms_per_launch'] > 0   # (what a sharded sample() pays per launch to agree on the next layout)
 
 
-def test_bench_eight_ranks_rehearsal_on_one_gpu_gloo():
-    """The launch the driver makes on an 8-GPU node, rehearsed on one GPU: eight ranks over gloo, each with its shard of the
-    chains (stream = global chain index), the barrier-bracketed timing with the maximum over the ranks, the summed leapfrog
-    count, the refit's exchange (the same 2 P rows on all eight ranks) and the cost of the per-launch layout vote."""
+def test_bench_four_ranks_rehearsal_on_one_gpu_gloo():
+    """The launch the driver makes on a multi-GPU node, rehearsed on one GPU: four ranks over gloo (four, so that with this
+    process no more than five processes hold the GPU at once), each with its shard of the chains (stream = global chain index),
+    the barrier-bracketed timing with the maximum over the ranks, the summed leapfrog count, the refit's exchange (the same 2 P
+    rows on all four ranks) and the cost of the per-launch layout vote."""
     port = 29300 + os.getpid() % 150
-    cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '8', '--master-addr', '127.0.0.1',
-           '--master-port', str(port), 'bench.py', '--gpus', '8', '--steps', '1', '--warmup', '1', '--chains', '128',
+    cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '4', '--master-addr', '127.0.0.1',
+           '--master-port', str(port), 'bench.py', '--gpus', '4', '--steps', '1', '--warmup', '1', '--chains', '128',
            '--backend', 'gloo', '--no-cpu-baseline']
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     j = _line(r.stdout)
-    assert j['n_gpus'] == 8 and j['scaling'] == 'weak' and j['value'] > 0 and j['config']['chains_per_gpu'] == 128
+    assert j['n_gpus'] == 4 and j['scaling'] == 'weak' and j['value'] > 0 and j['config']['chains_per_gpu'] == 128
     ex = j['refit_exchange']
     assert ex['collectives'] == 4 and ex['identical_on_all_ranks'] and ex['rows_selected'] == 4290 and ex['rows_per_rank'] == 128 * 100
     assert j['layout_vote']['ms_per_launch'] > 0

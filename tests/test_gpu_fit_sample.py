@@ -410,11 +410,12 @@ def test_decay_term_on_the_bounds_matrix(n_chain):
     assert same > 0.9, same
 
 
-@pytest.mark.parametrize('ipl,pipeline,n_rank', [(0, False, 2), (7, False, 2), (0, True, 2), (7, False, 8)])
+@pytest.mark.parametrize('ipl,pipeline,n_rank', [(0, False, 2), (7, False, 2), (0, True, 2), (7, False, 4)])
 def test_sample_two_ranks_equals_one_rank(tmp_path, ipl, pipeline, n_rank):
     """(ipl = 7: nine launches per round under layout 'auto' -- the layout of a launch is a pure function of the launches
-    before it, decided from the trees of ALL ranks' chains, so it is the same for one rank and for two.  n_rank = 8: the node's
-    launch rehearsed on one GPU -- ragged shards 3, 3, 3, 3, 3, 3, 2, 2 of the 22 chains, a layout vote per launch.)
+    before it, decided from the trees of ALL ranks' chains, so it is the same for one rank and for two.  n_rank = 4: a node's
+    launch rehearsed on one GPU -- ragged shards 6, 6, 5, 5 of the 22 chains, a layout vote per launch; four, so that with this
+    process no more than five processes hold the GPU at once.)
     sample() under torch.distributed (two ranks sharing the box's GPU over gloo, ragged shards 11 + 11 of 22 chains) returns
     exactly what one rank returns: x_0 and the xoshiro streams follow the global chain index, the trace's seed is resolved
     once and broadcast, and the warm start of the next round (_get_step_size, _get_metric) reduces over all ranks."""

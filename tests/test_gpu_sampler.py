@@ -912,9 +912,8 @@ def test_launches_may_alternate_between_the_layouts(ctx):
 def test_config5_four_wave_form_is_bit_identical_to_the_eight_wave_form(ctx, n_chain):
     """bf_sampler_kernel<8, ..., 17> (config 5's shard: four waves of 512 registers, each with a chain and two row tiles of S in
     registers for the whole launch) against <8, ..., 16> (eight waves, S streamed from L2 in every trip): samples, statistics,
-    adapted state, random streams and leapfrog counts EQUAL -- with one chain per workgroup (37 chains) and with four (600)."""
-    if _LAYOUT['v'] != 'group':
-        pytest.skip('does not depend on the module-wide layout parameter')
+    adapted state, random streams and leapfrog counts EQUAL -- with one chain per workgroup (37 chains) and with four (600).  The
+    chains request the module's layout: neither lane-per-chain kernel has the cubic terms, so every layout runs bf_sampler_kernel."""
     import bayesfast_amd as bfa
     from bayesfast_amd.chains import DeviceChains
     from bayesfast_amd.workloads import planck_like_logp
@@ -936,7 +935,7 @@ def test_config5_four_wave_form_is_bit_identical_to_the_eight_wave_form(ctx, n_c
             _lib.debug_set('cubic_form', form % 10 if form > 8 else form)
             _lib.debug_set('cubic_loops', int(form > 8))
             dc = DeviceChains(dd, x0, seed=5)
-            kw = dict(n_warmup=24, max_treedepth=5)
+            kw = dict(n_warmup=24, max_treedepth=5, layout=_LAYOUT['v'])
             s1, st1 = dc.run(24, 'NUTS', **kw)
             s2, st2 = dc.run(8, 'NUTS', **kw)
             out[form] = [t.cpu().numpy() for t in (s1, st1, s2, st2, dc.sc, dc.vec, dc.rng)] + [dc.total_leapfrog, _lib.last_kernel()]
@@ -953,9 +952,8 @@ def test_config5_four_wave_form_is_bit_identical_to_the_eight_wave_form(ctx, n_c
 def test_auto_layout_takes_the_wave_kernel_for_deep_trees_with_the_decay_term(ctx):
     """chains._deep_trees_prefer_waves: the common surrogate with the decay term at d = 64, trees in step -- 'auto' runs the group
     kernel while the trees have 7 leaves and the pipelined wave-per-chain kernel once they have 31 (the helper of the layout vote
-    reports the common tree size); the forced group layout gives the same trees and moments."""
-    if _LAYOUT['v'] != 'group':
-        pytest.skip('does not depend on the module-wide layout parameter')
+    reports the common tree size); the module's layout, forced, gives the same trees and moments (forced 'split' runs the group
+    kernel here: there is no split instantiation with the decay term)."""
     from bayesfast_amd.device import DeviceDensity
     from bayesfast_amd.chains import DeviceChains
     from bayesfast_amd.workloads import correlated_gaussian_spec
@@ -971,7 +969,8 @@ def test_auto_layout_takes_the_wave_kernel_for_deep_trees_with_the_decay_term(ct
     ts = _lib.NSTATS.index('tree_size')
     for ta, leaves, want in ((0.8, 7, 'in step'), (0.99, 31, 'wave')):
         out = {}
-        for lay in ('auto', 'group'):
+        forced = _LAYOUT['v']
+        for lay in ('auto', forced):
             dc = DeviceChains(dens, x0, seed=5)
             kw = dict(n_warmup=500, layout=lay, launch_iters=100, target_accept=ta)
             dc.run(500, 'NUTS', **kw)
@@ -981,15 +980,14 @@ def test_auto_layout_takes_the_wave_kernel_for_deep_trees_with_the_decay_term(ct
         assert (out['auto'][4] == 'wave') == (want == 'wave'), (ta, out['auto'][4:])   # ('split' falls back to the group kernel here)
         assert ('bf_nuts_pipe_kernel<4' if want == 'wave' else 'bf_group_kernel<4, true, 3>') in out['auto'][5], out['auto'][5]
         # (the lane-per-chain and the wave-per-chain kernels agree to rounding, not bit for bit: the same trees, the same moments)
-        assert np.median(out['group'][1][:, -50:, ts]) == leaves
-        np.testing.assert_allclose(out['auto'][0][:, -100:].var((0, 1)), out['group'][0][:, -100:].var((0, 1)), rtol=0.05)
+        assert np.median(out[forced][1][:, -50:, ts]) == leaves
+        np.testing.assert_allclose(out['auto'][0][:, -100:].var((0, 1)), out[forced][0][:, -100:].var((0, 1)), rtol=0.05)
 
 
 def test_auto_layout_runs_two_groups_per_cu_in_the_group_kernel_at_d32(ctx):
     """chains._two_groups_fit_a_cu: 32 chains per CU at 17 <= d <= 32 with the trees in step -- 'auto' runs the group kernel (two
-    workgroups per CU, a wave per SIMD) where it ran the split kernel (one), with the same results bit for bit."""
-    if _LAYOUT['v'] != 'group':
-        pytest.skip('does not depend on the module-wide layout parameter')
+    workgroups per CU, a wave per SIMD) where it ran the split kernel (one).  Against the module's layout, forced: the group and
+    the split kernel give the same results bit for bit, the wave layout the same trees and moments (it agrees to rounding)."""
     from bayesfast_amd.device import DeviceDensity
     from bayesfast_amd.chains import DeviceChains
     from bayesfast_amd.workloads import correlated_gaussian_spec
@@ -1001,16 +999,23 @@ def test_auto_layout_runs_two_groups_per_cu_in_the_group_kernel_at_d32(ctx):
     dens = DeviceDensity(spec, ctx)
     x0 = np.random.default_rng(4).normal(size=(n, d))
     out = {}
-    for lay in ('auto', 'split'):
+    forced = _LAYOUT['v']
+    for lay in ('auto', forced):
         dc = DeviceChains(dens, x0, seed=5)
         kw = dict(n_warmup=400, layout=lay, launch_iters=100)
         dc.run(400, 'NUTS', **kw)
         s, st = dc.run(200, 'NUTS', **kw)
         out[lay] = (s.cpu().numpy(), st.cpu().numpy(), dc.sc.cpu().numpy(), dc.rng.cpu().numpy(), dc.last_layout, _lib.last_kernel())
     assert out['auto'][4] == 'group' and 'bf_group_kernel<2' in out['auto'][5], out['auto'][4:]
-    assert out['split'][4] == 'split' and 'bf_split_kernel<2' in out['split'][5]
-    for a, b in zip(out['auto'][:4], out['split'][:4]):
-        assert np.array_equal(a, b, equal_nan=True)
+    assert out[forced][4] == forced, out[forced][4:]
+    if forced == 'wave':
+        ts = _lib.NSTATS.index('tree_size')
+        assert np.median(out['wave'][1][:, -50:, ts]) == np.median(out['auto'][1][:, -50:, ts])
+        np.testing.assert_allclose(out['auto'][0][:, -100:].var((0, 1)), out['wave'][0][:, -100:].var((0, 1)), rtol=0.05)
+    else:
+        assert 'bf_%s_kernel<2' % forced in out[forced][5], out[forced][5]
+        for a, b in zip(out['auto'][:4], out[forced][:4]):
+            assert np.array_equal(a, b, equal_nan=True)
 
 
 @pytest.mark.parametrize('case', ['plain', 'decay_out'])

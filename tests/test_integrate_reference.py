@@ -1,8 +1,8 @@
 """The drop-in seam (bayesfast_amd/integrate.py) under the REFERENCE's own code.
 
-Container-only: these tests import the reference package (built from /root/reference into a scratch directory by
-tests/golden/make_golden.py's recipe) and are skipped wherever it does not exist -- the reference never travels to the GPU
-box.  There is no GPU here either, so the device entry points (DeviceChains, DeviceDensity, the device fit) are swapped, IN
+These tests import the reference package that build() compiled into oracle/_ref/ (oracle/reference.py: the reference's
+Python package and its Cython extensions; a build product, never in git) and are skipped wherever build() found no checkout of
+the reference to compile.  They need no GPU: the device entry points (DeviceChains, DeviceDensity, the device fit) are swapped, IN
 THESE TESTS ONLY, for stand-ins backed by the CPU oracle (tests/helpers/oracle_standin.py); everything else -- the seam's
 subclasses, adapters, trace conversion, sample(), TraceTuple -- is the shipped code, driven by the reference's Recipe,
 Density, _get_step_size and _get_metric.  The GPU side of the same workload is tests/test_gpu_recipe.py."""
@@ -13,16 +13,16 @@ import sys
 import numpy as np
 import pytest
 
+from oracle import reference
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, 'helpers'))
-REF = '/root/reference'
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'bayesfast')), reason='needs the reference at /root/reference')
+pytestmark = pytest.mark.skipif(not reference.is_built(), reason='needs the reference built into oracle/_ref by build()')
 
 
 @pytest.fixture(scope='module')
 def bf():
-    import make_golden
-    return make_golden.prepare_reference(REF, os.environ.get('BF_REF_WORK', '/tmp/bfref'))
+    return reference.load()
 
 
 @pytest.fixture()

@@ -524,6 +524,7 @@ def config3_rounds(ctx, seed, chains, iters, n_adapt, steps, warmup, rank=0, wor
     (round 1).  `steps` timed launches of `iters` NUTS iterations in round 0 and `steps_round1` (default: the same) in round 1, each
     round after `n_adapt` adaptation iterations and `warmup` untimed launches.  value = leapfrogs of both rounds' timed launches /
     their time (max over ranks is the caller's business: `wall_s_timed` per round); the fits and the selection are timed beside it.
+    `outputs`: (samples, stats) device tensors of each round's last launch, what a caller of the sampler receives.
     Departure from SURVEY 8d, stated on the line: the density carries the decay term the reference's GBS recipes use
     (core/density.py:740-746) -- without it the chains run away along the first fit's indefinite quadratic form."""
     import torch
@@ -563,7 +564,7 @@ def config3_rounds(ctx, seed, chains, iters, n_adapt, steps, warmup, rank=0, wor
     cpu_rounds = [dict(zip(('spec', 'x_start', 'step_size', 'var'), cpu_job(ch0, den.spec(), d)), target_accept=0.8,
                        leapfrogs=r0['leapfrogs_timed'])] if cpu_seconds > 0 else []
     if round0_only:
-        return {'rounds': [r0], 'refit': dict(t_ms), 'value': r0['value']}
+        return {'rounds': [r0], 'outputs': [(s, st)], 'refit': dict(t_ms), 'value': r0['value']}
     # one refit cycle (core/recipe.py:1074-1155 without the cut-off): 2 P of ALL ranks' round-0 rows by their logq; every rank sorts
     # its own shard, four collectives move quantile keys, counts, candidates and the selected rows (identical on every rank)
     n_rows = C * iters
@@ -581,9 +582,9 @@ def config3_rounds(ctx, seed, chains, iters, n_adapt, steps, warmup, rank=0, wor
     # round 1 starts where the reference's recipe starts it: on rows of the refit set (core/recipe.py:1028-1044 hands the previous
     # round's samples on); one global choice sliced per rank
     pick = np.random.default_rng(seed + 2).integers(0, x_new.shape[0], world * C)[rank * C:(rank + 1) * C]
-    r1, _, _ = _sampler_block(ctx, den, x_new[pick], seed + 1, 0.8, n_adapt, iters, steps_round1 or steps, 0., what % 1, **common)
+    r1, s1, st1 = _sampler_block(ctx, den, x_new[pick], seed + 1, 0.8, n_adapt, iters, steps_round1 or steps, 0., what % 1, **common)
     ch1 = r1.pop('_chains')
-    out = {'rounds': [r0, r1],
+    out = {'rounds': [r0, r1], 'outputs': [(s, st), (s1, st1)],
            'refit': dict(t_ms, n_fit_points=int(x_new.shape[0]), wire_bytes_per_rank=int(est.get('wire_bytes', 0)),
                          collectives=int(est.get('collectives', 0))),
            'value': (r0['leapfrogs_timed'] + r1['leapfrogs_timed']) / (r0['wall_s_timed'] + r1['wall_s_timed']),
