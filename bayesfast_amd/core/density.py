@@ -75,7 +75,7 @@ class SurrogateDensity:
         self._hard_bounds = np.ascontiguousarray(hb)
         self.set_decay_options(**(decay_options or {}))
         self._mu = self._hess = None
-        self._device = None
+        self._device = self._device_key = None
 
     input_size = property(lambda self: self._d)
 
@@ -223,9 +223,15 @@ class SurrogateDensity:
         return spec
 
     def device(self, ctx=None):
+        """The density on the GPU (``DeviceDensity``), cached.  Rebuilt when the density's own options change (``fit`` and
+        ``set_decay_options`` drop it), when the surrogate's coefficients or bound change, including through ``self.surrogate``
+        directly (``PolyModel._device_key``), and for another ``ctx``."""
         from ..device import DeviceDensity
-        if self._device is None or (ctx is not None and self._device.ctx is not ctx):
+        key = self.surrogate._device_key()
+        if (self._device is None or getattr(self, '_device_key', None) != key
+                or (ctx is not None and self._device.ctx is not ctx)):
             self._device = DeviceDensity(self.spec(), ctx)
+            self._device_key = key
         return self._device
 
     def logp_and_grad(self, x, original_space=True):

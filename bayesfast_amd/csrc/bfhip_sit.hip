@@ -922,10 +922,13 @@ extern "C" int bfhip_polar_ns(bfhip_ctx *ctx, int d, const double *a, double *x,
         unsigned long long *slots = (unsigned long long *)((char *)counter + 64);
         if (nt <= BF_POLAR_LDS_MAXT && bf_tune().polar_tiles != 2) {
             const size_t lds_x = ((size_t)(16 * nt + 16) * (16 * nt + 4) + 2 * BF_POLAR_LDS_MAXT) * sizeof(double);   // 152 KB at d = 128
-            static size_t lds_set = 0;
-            if (lds_x > lds_set) {
+            // (the attribute belongs to the kernel on ONE device: raised once per device, as bfhip_sampler.hip does it; devices past the
+            // table set it at every call)
+            static size_t lds_set[64];
+            const bool slot = ctx->device >= 0 && ctx->device < 64;
+            if (!slot || lds_x > lds_set[ctx->device]) {
                 BF_HIP_CHECK(hipFuncSetAttribute((const void *)bf_polar_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x));
-                lds_set = lds_x;
+                if (slot) lds_set[ctx->device] = lds_x;
             }
             hipLaunchKernelGGL(bf_polar_lds_kernel, dim3(nt), dim3(64 * nt), lds_x, ctx->stream, d, a, x, n_iter, work, resid, counter, slots,
                                bf_tune().gstamps);

@@ -40,6 +40,7 @@ class PolyConfig:
         self._set_input_mask(input_mask)
         self._set_output_mask(output_mask)
         self._coef = None
+        self._gen = 0   # bumped by every write of _coef (PolyModel.device_model keys its device copy on it)
 
     order = property(lambda self: self._order)
     input_mask = property(lambda self: self._input_mask)
@@ -112,6 +113,7 @@ class PolyConfig:
         if self._coef is None:
             self._coef = np.zeros(self._A_shape)
         self._coef[i] = coefi
+        self._gen = getattr(self, '_gen', 0) + 1
 
 
 class PolyModel(Surrogate):
@@ -162,6 +164,7 @@ class PolyModel(Surrogate):
 
     def set_bound_options(self, use_bound=True, alpha=None, alpha_p=100., center_max=True):
         """Linear extrapolation options far away from the fit points (modules/poly.py:232-260)."""
+        self._touch()
         self._use_bound = bool(use_bound)
         if alpha is None:
             self._alpha = None
@@ -184,6 +187,16 @@ class PolyModel(Surrogate):
                 raise ValueError('invalid value for alpha_p.')
             self._alpha_p = alpha_p
         self._center_max = bool(center_max)
+
+    def _touch(self):
+        """Record a change of the model's own state (bound options and statistics, a fit): device copies built before are stale."""
+        self._gen = getattr(self, '_gen', 0) + 1
+
+    def _device_key(self, use_bound=None):
+        """What a device copy of ``poly_spec(use_bound)`` was built from: the model's generation, every config's coefficient
+        generation (``PolyConfig._set``) and the bound as ``poly_spec`` resolves it.  Equal keys, equal specs."""
+        ub = (self._use_bound and not self._all_linear) if use_bound is None else bool(use_bound)
+        return (getattr(self, '_gen', 0), ub) + tuple(getattr(c, '_gen', 0) for c in self._configs)
 
     def _build_recipe(self):
         """(output, order) -> config index table with the reference's overlap checks (modules/poly.py:298-338)."""
@@ -243,9 +256,9 @@ class PolyModel(Surrogate):
 
     def device_model(self, use_bound=None):
         """The multi-output module on the GPU (``DevicePolyModel``): batched ``fun_and_jac`` in one launch.  Rebuilt
-        after every fit."""
+        after every change of the coefficients or the bound (``_device_key``)."""
         from ..device import DevicePolyModel
-        key = (id(self._configs[0]._coef), use_bound)
+        key = self._device_key(use_bound)
         if getattr(self, '_dev_model_key', None) != key:
             self._dev_model = DevicePolyModel(self.poly_spec(use_bound))
             self._dev_model_key = key
@@ -363,10 +376,9 @@ class PolyModel(Surrogate):
                     c._set(sol[k:k + wd, jo], qq)
                     k += wd
         del pending
-        self._dev_model_key = None  # the device copy of the module is stale now
+        self._touch()   # a refit: every device copy built before it is stale
         if bound is not None:
             self._apply_bound(*bound)
-        self._dev_model_key = None
 
     def _bound_stats(self, x, logp=None):
         """The part of ``_set_bound`` that only needs the fit points: mu, H = inv(cov), alpha and the point f_mu is taken at
@@ -404,6 +416,7 @@ class PolyModel(Surrogate):
         if alpha is not None:
             self._alpha = alpha
         self._f_mu = self._device_eval(mu_f, use_bound=False)[0]  # (modules/poly.py:277-292: the fitted model at mu_f)
+        self._touch()
 
     def _set_bound(self, x, logp=None):
         """mu, H = inv(cov), alpha and f_mu of the extrapolation bound (modules/poly.py:262-292)."""

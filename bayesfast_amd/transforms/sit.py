@@ -52,6 +52,7 @@ class SIT:
         self._data = None
         self._tables = []
         self._A = self._B = self._m = self._logdetA = None
+        self._dev_rot = None
 
     @classmethod
     def _from_parts(cls, A, B, m, logdetA, splines):
@@ -219,6 +220,14 @@ class SIT:
                 splines[j] = sp
         return splines
 
+    def _start_fit(self, d):
+        """Drop the fitted iterations, and with them the device copies of the rotations: a new fit of the same ``n_iter``
+        reaches the same ``i_iter``, so the cache's key alone would not tell the new rotations from the old ones."""
+        self._tables = []
+        self._A, self._B = np.zeros((0, d, d)), np.zeros((0, d, d))
+        self._m, self._logdetA = np.zeros((0, d)), np.zeros(0)
+        self._dev_rot = None
+
     def fit(self, data=None, weights=None, n_run=None):
         """transforms/sit.py:257-341 (without the plots)."""
         from ..utils.threads import blas_single_thread
@@ -245,10 +254,7 @@ class SIT:
                 self._weights = np.ones(n) / n
             self._data = ctx.tensor(data).clone()
             self._data_init = None
-            d = data.shape[-1]
-            self._tables = []
-            self._A, self._B = np.zeros((0, d, d)), np.zeros((0, d, d))
-            self._m, self._logdetA = np.zeros((0, d)), np.zeros(0)
+            self._start_fit(data.shape[-1])
         elif data is not None:
             try:
                 data = np.array(data, dtype=np.float64)
@@ -273,10 +279,7 @@ class SIT:
                 self._weights = np.ones(n) / n
             self._data = ctx.tensor(data)
             self._data_init = data.copy()
-            d = data.shape[-1]
-            self._tables = []
-            self._A, self._B = np.zeros((0, d, d)), np.zeros((0, d, d))
-            self._m, self._logdetA = np.zeros((0, d)), np.zeros(0)
+            self._start_fit(data.shape[-1])
         elif self._data is None:
             raise ValueError('you have not given me the data to fit.')
         if n_run is None:
@@ -321,7 +324,8 @@ class SIT:
         return y.reshape((-1, y.shape[-1])), y.shape
 
     def _rotations_on_device(self):
-        """The iterations' means and rotation matrices as device tensors (cached per fitted iteration count)."""
+        """The iterations' means and rotation matrices as device tensors (cached per fitted iteration count; a new fit clears the
+        cache, ``_start_fit``)."""
         ctx = self._ctx()
         c = getattr(self, '_dev_rot', None)
         if c is None or c[0] != self.i_iter or c[1] is not ctx:
