@@ -13,7 +13,8 @@ from .samplers import NTrace, HTrace, TNTrace, GaussianBase, TraceTuple
 from .utils import SystematicResampler
 from .core.refit import select_fit_points, importance_weights
 from .transforms import SIT
-from .evidence import GBS, bridge
+from .evidence import GBS, GIS, GHM, bridge, importance, harmonic
 
 __all__ = ['PolyConfig', 'PolyModel', 'Surrogate', 'SurrogateDensity', 'Chi2PipelineDensity', 'GaussianLink', 'sample', 'NTrace', 'HTrace', 'TNTrace', 'GaussianBase', 'TraceTuple',
-           'SystematicResampler', 'select_fit_points', 'importance_weights', 'SIT', 'GBS', 'bridge']
+           'SystematicResampler', 'select_fit_points', 'importance_weights', 'SIT', 'GBS', 'GIS', 'GHM', 'bridge', 'importance',
+           'harmonic']

@@ -111,6 +111,7 @@ SYMBOLS = {
     'bfhip_spline_apply': (C.c_int, [_vp, C.c_int, C.c_long, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     'bfhip_bridge_sums': (C.c_int, [_vp, C.c_long, _vp, C.c_long, _vp, C.c_double, _vp]),
     'bfhip_bridge_terms': (C.c_int, [_vp, C.c_long, _vp, _vp, C.c_long, _vp, _vp, C.c_double, _vp, _vp]),
+    'bfhip_logmeanexp_stats': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

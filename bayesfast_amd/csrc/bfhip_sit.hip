@@ -9,6 +9,8 @@
 //                        for a batch of points: SIT.forward_transform / backward_transform / logq
 //   bfhip_bridge_sums    the two log-sum-exp terms of the bridge estimator's score function (evidence/bridge.py:44-49)
 //   bfhip_bridge_terms   the per-sample terms f1, f2 of its error estimate (:52-57)
+//   bfhip_logmeanexp_stats  log(mean exp(x - y)) and the mean and variance of the normalised terms: importance sampling
+//                        (evidence/importance.py:26-28) and the harmonic mean (evidence/harmonic.py:27-31)
 //
 // HBM-/ALU-bound elementwise and reduction work in float64; every reduction has a fixed order (per-block partial sums
 // combined by one thread), so results do not depend on the launch.
@@ -267,6 +269,119 @@ extern "C" int bfhip_bridge_terms(bfhip_ctx *ctx, long n_p, const double *logp_p
     const long nmax = n_p > n_q ? n_p : n_q;
     hipLaunchKernelGGL(bf_bridge_terms_kernel, dim3((unsigned)((nmax + 255) / 256)), dim3(256), 0, ctx->stream, n_p, logp_p, logq_p, n_q,
                        logp_q, logq_q, logr, f1, f2);
+    BF_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- log-mean-exp and the moments of the normalised terms (evidence/importance.py:26-28, evidence/harmonic.py:27-31) --------
+// t_i = x_i - y_i.  Pass 1: a running (max, sum) per thread, merged over the block and written to a slab of partials; one block
+// combines them to L = log(mean_i exp(t_i)).  Pass 2: f_i = exp(t_i - L), a Chan/Welford (count, mean, M2) per thread, merged the
+// same way; the variance is M2 / n (no n sum f^2 / (sum f)^2 - 1: that cancels when q fits p well).  The grid depends on n only
+// and every merge has a fixed order, so two calls on the same inputs are bitwise equal.
+#define LME_TH 256
+#define LME_MAXB 512
+// (m1, s1) <- the pair for the union of both sets: sum exp(. - m) with m the larger max; an equal max scales by exactly 1, which
+// keeps -inf (no terms yet) and +inf (scipy's logsumexp gives +inf) out of exp(inf - inf)
+__device__ inline void bf_ms_merge(double &m1, double &s1, double m2, double s2) {
+    const double mm = m1 > m2 ? m1 : m2;
+    s1 = (m1 == mm ? s1 : s1 * exp(m1 - mm)) + (m2 == mm ? s2 : s2 * exp(m2 - mm));
+    m1 = mm;
+}
+__device__ inline void bf_ms_block(double mx, double sm, double *rm, double *rs) {  // -> rm[0], rs[0]
+    rm[threadIdx.x] = mx;
+    rs[threadIdx.x] = sm;
+    __syncthreads();
+    for (int o = LME_TH / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            double m = rm[threadIdx.x], s = rs[threadIdx.x];
+            bf_ms_merge(m, s, rm[threadIdx.x + o], rs[threadIdx.x + o]);
+            rm[threadIdx.x] = m;
+            rs[threadIdx.x] = s;
+        }
+        __syncthreads();
+    }
+}
+// Chan et al.'s pairwise update of (count, mean, M2)
+__device__ inline void bf_welford_merge(double &c1, double &m1, double &q1, double c2, double m2, double q2) {
+    if (c2 == 0.) return;
+    if (c1 == 0.) { c1 = c2; m1 = m2; q1 = q2; return; }
+    const double c = c1 + c2, dl = m2 - m1;
+    m1 += dl * (c2 / c);
+    q1 += q2 + dl * dl * (c1 * c2 / c);
+    c1 = c;
+}
+__device__ inline void bf_welford_block(double c, double m, double q, double *rc, double *rm, double *rq) {  // -> rc[0], rm[0], rq[0]
+    rc[threadIdx.x] = c;
+    rm[threadIdx.x] = m;
+    rq[threadIdx.x] = q;
+    __syncthreads();
+    for (int o = LME_TH / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            double c1 = rc[threadIdx.x], m1 = rm[threadIdx.x], q1 = rq[threadIdx.x];
+            bf_welford_merge(c1, m1, q1, rc[threadIdx.x + o], rm[threadIdx.x + o], rq[threadIdx.x + o]);
+            rc[threadIdx.x] = c1;
+            rm[threadIdx.x] = m1;
+            rq[threadIdx.x] = q1;
+        }
+        __syncthreads();
+    }
+}
+__global__ __launch_bounds__(LME_TH) void bf_lme_part_kernel(long n, const double *__restrict__ x, const double *__restrict__ y,
+                                                            double *__restrict__ part) {
+    __shared__ double rm[LME_TH], rs[LME_TH];
+    double mx = -INFINITY, sm = 0.;
+    for (long i = (long)blockIdx.x * LME_TH + threadIdx.x; i < n; i += (long)gridDim.x * LME_TH) {
+        const double t = x[i] - y[i];
+        if (t > mx) { sm = sm * exp(mx - t) + 1.; mx = t; }        // (mx = -inf: exp(-inf) = 0; a NaN sum stays NaN)
+        else if (t > -INFINITY) sm += (t == mx) ? 1. : exp(t - mx);
+        else if (t != t) sm = NAN;                                  // -inf is a zero weight, NaN propagates
+    }
+    bf_ms_block(mx, sm, rm, rs);
+    if (threadIdx.x == 0) { part[2 * blockIdx.x] = rm[0]; part[2 * blockIdx.x + 1] = rs[0]; }
+}
+// one block of LME_TH threads: thread j merges partials j and j + LME_TH, then the block tree
+__global__ __launch_bounds__(LME_TH) void bf_lme_combine_kernel(int nb, long n, const double *__restrict__ part, double *__restrict__ out3) {
+    __shared__ double rm[LME_TH], rs[LME_TH];
+    double mx = -INFINITY, sm = 0.;
+    for (int b = threadIdx.x; b < nb; b += LME_TH) bf_ms_merge(mx, sm, part[2 * b], part[2 * b + 1]);
+    bf_ms_block(mx, sm, rm, rs);
+    if (threadIdx.x == 0) out3[0] = rm[0] + log(rs[0] / (double)n);  // all -inf: -inf + log(0) = -inf
+}
+__global__ __launch_bounds__(LME_TH) void bf_lme_moments_kernel(long n, const double *__restrict__ x, const double *__restrict__ y,
+                                                               const double *__restrict__ out3, double *__restrict__ terms,
+                                                               double *__restrict__ part) {
+    __shared__ double rc[LME_TH], rm[LME_TH], rq[LME_TH];
+    const double L = out3[0];
+    double c = 0., m = 0., q = 0.;
+    for (long i = (long)blockIdx.x * LME_TH + threadIdx.x; i < n; i += (long)gridDim.x * LME_TH) {
+        const double f = exp((x[i] - y[i]) - L);
+        if (terms) terms[i] = f;
+        c += 1.;
+        const double dl = f - m;
+        m += dl / c;
+        q += dl * (f - m);
+    }
+    bf_welford_block(c, m, q, rc, rm, rq);
+    if (threadIdx.x == 0) { part[3 * blockIdx.x] = rc[0]; part[3 * blockIdx.x + 1] = rm[0]; part[3 * blockIdx.x + 2] = rq[0]; }
+}
+__global__ __launch_bounds__(LME_TH) void bf_lme_moments_combine_kernel(int nb, const double *__restrict__ part, double *__restrict__ out3) {
+    __shared__ double rc[LME_TH], rm[LME_TH], rq[LME_TH];
+    double c = 0., m = 0., q = 0.;
+    for (int b = threadIdx.x; b < nb; b += LME_TH) bf_welford_merge(c, m, q, part[3 * b], part[3 * b + 1], part[3 * b + 2]);
+    bf_welford_block(c, m, q, rc, rm, rq);
+    if (threadIdx.x == 0) { out3[1] = rm[0]; out3[2] = rq[0] / rc[0]; }
+}
+
+extern "C" int bfhip_logmeanexp_stats(bfhip_ctx *ctx, long n, const double *x, const double *y, double *out3, double *terms) {
+    BfDeviceGuard dev_guard(ctx);
+    if (!ctx || n < 1 || !x || !y || !out3) return bf_set_error(BFHIP_ERR_ARG, "bfhip_logmeanexp_stats: invalid argument");
+    const int nb = (int)((n + LME_TH - 1) / LME_TH < LME_MAXB ? (n + LME_TH - 1) / LME_TH : LME_MAXB);
+    if (int rc = ensure_ws(ctx, (size_t)5 * nb * sizeof(double))) return rc;
+    double *part = (double *)ctx->scratch, *part2 = part + 2 * nb;
+    hipLaunchKernelGGL(bf_lme_part_kernel, dim3(nb), dim3(LME_TH), 0, ctx->stream, n, x, y, part);
+    hipLaunchKernelGGL(bf_lme_combine_kernel, dim3(1), dim3(LME_TH), 0, ctx->stream, nb, n, part, out3);
+    hipLaunchKernelGGL(bf_lme_moments_kernel, dim3(nb), dim3(LME_TH), 0, ctx->stream, n, x, y, out3, terms, part2);
+    hipLaunchKernelGGL(bf_lme_moments_combine_kernel, dim3(1), dim3(LME_TH), 0, ctx->stream, nb, part2, out3);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -1,4 +1,7 @@
 from .bridge import bridge
+from .importance import importance
+from .harmonic import harmonic
 from .gbs import GBS
+from .gaussianized_q import GIS, GHM
 
-__all__ = ['bridge', 'GBS']
+__all__ = ['bridge', 'importance', 'harmonic', 'GBS', 'GIS', 'GHM']

@@ -434,6 +434,13 @@ int bfhip_bridge_sums(bfhip_ctx *ctx, long n_a, const double *a, long n_b, const
 int bfhip_bridge_terms(bfhip_ctx *ctx, long n_p, const double *logp_p, const double *logq_p, long n_q, const double *logp_q,
                        const double *logq_q, double logr, double *f1, double *f2);
 
+/* Importance sampling (evidence/importance.py:26-28, x = logp_q, y = logq_q) and the harmonic mean (evidence/harmonic.py:27-31,
+ * x = logq_p, y = logp_p, log r = -L): with t_i = x_i - y_i (i < n), out3[0] = L = log(mean_i exp(t_i)); out3[1] = mean_i f_i,
+ * out3[2] = population variance of f_i (numpy's ddof = 0), where f_i = exp(t_i - L); terms (may be NULL) receives f_i.
+ * -inf in t is a zero weight, NaN propagates; when every t_i is -inf, L = -inf and the moments are NaN.  Fixed-order reductions
+ * (bitwise repeatable), stream-ordered, no host synchronisation. */
+int bfhip_logmeanexp_stats(bfhip_ctx *ctx, long n, const double *x, const double *y, double *out3, double *terms);
+
 /* The glue of one FastICA iteration (scikit-learn's _ica_par, logcosh contrast, as SIT calls it: transforms/sit.py:235-244) around
  * the caller's two products Y = X1 W^T and P[b] = G_b^T X1_b (row batches b) and bfhip_polar_ns:
  *   bfhip_ica_tanh      y (n_pad,d) <- tanh(y) in place; partial (ceil(n_pad / 32), d) <- column sums of 1 - tanh(y)^2 over the
