@@ -126,7 +126,9 @@ __global__ void bf_iw_clip_kernel(long n, const double *__restrict__ w, const do
     const double cap = (tot / (double)n) * pow((double)n, k_trunc);
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const double v = w[i];
-        wt[i] = k_trunc < 0. ? v : (v < 0. ? 0. : (v > cap ? cap : v));  // np.clip(w, 0, cap) (NaN stays)
+        // np.clip(w, 0, cap) propagates NaN from either side: a NaN weight stays NaN, and a NaN cap (some weight was NaN)
+        // makes every truncated weight NaN
+        wt[i] = k_trunc < 0. ? v : (cap != cap ? cap : (v < 0. ? 0. : (v > cap ? cap : v)));
     }
 }
 

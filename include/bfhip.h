@@ -388,7 +388,8 @@ int bfhip_order_keys(bfhip_ctx *ctx, long n, const double *a, uint64_t *keys);
 int bfhip_count_keys(bfhip_ctx *ctx, long n, const uint64_t *keys_sorted, long nq, const uint64_t *q, int upper, int64_t *counts);
 
 /* PostStep's importance weights (core/recipe.py:1289-1296): w = exp(logp - logq), w_trunc = clip(w, 0, mean(w) n^k_trunc)
- * (w_trunc = w for k_trunc < 0); all arrays (n,) float64 on the device. */
+ * (w_trunc = w for k_trunc < 0) with np.clip's NaN semantics: one NaN weight makes every w_trunc NaN; all arrays (n,) float64
+ * on the device. */
 int bfhip_importance_weights(bfhip_ctx *ctx, long n, const double *logp, const double *logq, double k_trunc, double *w,
                              double *w_trunc);
 
