@@ -267,7 +267,9 @@ class Chi2PipelineDensity(SurrogateDensity):
     input_scales, hard_bounds, decay_options : as ``SurrogateDensity``
 
     ``sample(density, ...)`` runs NUTS / HMC on it inside the fused kernel (``bfhip_pipeline_upload``: the (m, d) Jacobian is
-    never formed; two FP64-MFMA contractions per gradient, bayesfast_amd/csrc/bfhip_pld.h).  ``logp_and_grad_device`` keeps
+    never formed; two FP64-MFMA contractions per gradient, bayesfast_amd/csrc/bfhip_pld.h; a surrogate whose monomials do not fit a
+    workgroup's LDS is streamed through it in chunks, up to min(output_size, monomials) = 1024 -- beyond that, and above 128 inputs,
+    the upload raises NotImplementedError).  ``logp_and_grad_device`` keeps
     the first implementation -- ``bfhip_polymodel_eval`` (f and the (n, m, d) Jacobians) + ``bfhip_chi2_stage`` -- as an
     independent second route the tests compare with."""
 

@@ -108,7 +108,7 @@ int bf_launch_split(bfhip_ctx *ctx, const SamplerArgs &args_in) {
 
 // LDS bytes of the group kernel on the pipeline density (0: not a pipeline density)
 static size_t group_pld_lds_bytes(const DevModel &m) {
-    if (!m.pld.on) return 0;
+    if (!m.pld.on || m.pld.stream) return 0;
     const int W = m.DP / 16;
     const size_t own = W == 4 ? GroupGeo<4>::lds_doubles(1) : (W == 2 ? GroupGeo<2>::lds_doubles(1) : GroupGeo<1>::lds_doubles(1));
     // (one operand region -- no decay term here --, K-split 1 of the second contraction and the row-major copy of C': bfhip_group.h)
@@ -117,7 +117,7 @@ static size_t group_pld_lds_bytes(const DevModel &m) {
 
 bool bf_group_supports(const DevModel &m, const SamplerArgs &args) {
     if (m.pld.on)   // the pipeline density (round 6): NUTS, no decay term, the sixteen-chain LDS layout has to fit beside the tree vectors
-        return m.DP <= 64 && args.cfg.sampler == 0 && !m.use_decay && !args.mat && !(bf_tune().no_group_pld != 0) &&
+        return !m.pld.stream && m.DP <= 64 && args.cfg.sampler == 0 && !m.use_decay && !args.mat && !(bf_tune().no_group_pld != 0) &&
                group_pld_lds_bytes(m) <= (size_t)160 * 1024;
     return m.DP <= 64 && m.has_quad && m.use_bound && !m.has_su && !m.has_cubic && !m.has_link && !args.mat;
 }

@@ -53,6 +53,13 @@ struct PldDev {
     const unsigned long long *gtab;   // [n_ent][DP]: low word = monomial p, high word = a | b << 8 | mult << 16 (padding: a = DP + 1)
     const double *prior_mu, *prior_prec;   // (DP) original-space Gaussian prior, zero padded (prec 0 = no prior on that input)
     double logp0, prior_c0;
+    // streamed form (bfhip_pld.h: pld_eval_stream_q8), taken where the resident LDS block does not fit (or pld_stream = 1); then
+    // CF, CTF and gtab are NULL, KS2 = 1, n_ent = 0, PP = NC KC and only the eight-chain forms run it
+    int stream;             // the monomials are streamed in NC chunks of KC
+    int KC, NC;             // monomials per chunk (a multiple of 16) and chunks
+    int n_entc;             // entries per chunk and dimension of the chunked gradient table
+    const double *CS;       // [NC][NT1][KC / 16][256] C' in 16 x 16 blocks, chunk-major (bfhip_pld.h: pld_cs_index)
+    const unsigned long long *gtabc;   // [NC][n_entc][DP]: as gtab, with p the monomial's index within its chunk
 };
 
 

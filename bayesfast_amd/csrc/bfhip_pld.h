@@ -58,6 +58,20 @@ __host__ __device__ inline size_t pld_lds_doubles(int DP, int MP, int PP, int KS
     return (size_t)16 * (DP + 2) + 16 + (size_t)2 * MP + (size_t)32 * n_red + ns2 * xs + (size_t)KS2 * ns1 * xs + (size_t)n_ent * DP + PP / 2;
 }
 
+// The streamed form's block (pld_s_lds, eight chains): XE [8][DP + 2] | CH [16] | YW [2][MP] | RED [8][2][16] | RB [MP / 4][33] |
+// BUF [2][KC / 4][33], the double buffer of the Phi chunks in the first pass and of the W chunks in the second
+#define PLD_S_TPW 8   // row tiles of GEMM1 per wave held in registers across the chunks: min(m, nf) <= 16 * 8 * PLD_S_TPW
+__host__ __device__ inline size_t pld_s_lds_doubles(int DP, int MP, int KC) {
+    return (size_t)8 * (DP + 2) + 16 + (size_t)2 * MP + 256 + (size_t)(MP / 4) * PLD_XS8 + (size_t)2 * (KC / 4) * PLD_XS8;
+}
+// where element (o, p) of C' sits in the streamed form's copy (PldDev::CS): 16 x 16 blocks [chunk][o / 16][p % KC / 16], and in
+// a block the 4 x 4 sub-blocks [o / 4 % 4][p / 4 % 4], each row-major.  Both contractions read whole 128-byte sub-blocks: GEMM1's
+// k-step (16 rows o, 4 columns p) is one sub-block column, GEMM2's (4 rows o, 16 columns p) one sub-block row -- one copy of C'.
+__host__ __device__ inline size_t pld_cs_index(int o, int p, int MP, int KC) {
+    const int c = p / KC, pl = p % KC;
+    return (size_t)c * MP * KC + (size_t)(o >> 4) * 16 * KC + (size_t)(pl >> 4) * 256 + ((o >> 2) & 3) * 64 + ((pl >> 2) & 3) * 16 + (o & 3) * 4 + (pl & 3);
+}
+
 #ifndef BF_HOST_EMU
 __device__ inline PldLds pld_lds(double *base, int DP, const PldDev &pl, int cw = 16, bool with_cl = false, int n_red = 16) {
     PldLds L;
@@ -605,5 +619,184 @@ __device__ inline double pld_grad(const PldDev &pl, const PldLds &L, int DP, int
         g += (mult * wv) * (xe[eh & 255u] * xe[(eh >> 8) & 255u]);
     }
     return g;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Streamed form (eight chains, eight waves): the monomials in NC chunks of KC, for surrogates whose resident block -- Phi, W and
+// the gradient table for every monomial -- does not fit a workgroup's LDS.  Two passes over the chunks:
+//   pass 1  chunk c of Phi (the chains' waves) -> GEMM1 k-steps of the chunk, F row tiles accumulated in registers (PLD_S_TPW per
+//           wave); after the last chunk today's epilogue (bound extrapolation, r = F - y', the RED sums) writes r to RB
+//   pass 2  W rows of chunk c = C'^T r over the full K = MP -> the chains' waves gather (J_0^T r)_dim from the chunk's gradient
+//           table, one register per dimension, in increasing p as pld_grad does
+// Phi chunks and W chunks take turns in one double buffer (BUF): one workgroup barrier per chunk.  No atomics; every sum has a
+// fixed order.  C' is read from PldDev::CS (pld_cs_index), the chunk's gradient table from global memory.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ inline PldLds pld_s_lds(double *base, int DP, const PldDev &pl) {
+    PldLds L;
+    L.CW = 8;
+    L.XS = PLD_XS8;
+    L.XE = base;
+    L.CH = L.XE + 8 * (DP + 2);
+    L.YW = L.CH + 16;
+    L.RED = L.YW + 2 * pl.MP;
+    L.RB = L.RED + 256;
+    L.PHI = L.RB + (size_t)(pl.MP / 4) * PLD_XS8;   // BUF: [2][KC / 4][33]
+    L.WX = nullptr;
+    L.GT = nullptr;
+    L.MONO = nullptr;
+    L.CL = nullptr;
+    L.CLS = 0;
+    return L;
+}
+
+__device__ inline void pld_s_stage(const PldDev &pl, const PldLds &L, int tid, int nth) {
+    for (int i = tid; i < pl.MP; i += nth) {
+        L.YW[i] = pl.yw[i];
+        L.YW[pl.MP + i] = pl.fmuw[i];
+    }
+}
+
+// chain wave c: its evaluation point (then 1 and 0) and beta; the monomials follow chunk by chunk (pld_s_phi)
+template <int E>
+__device__ inline void pld_s_point(const PldLds &L, int DP, int c, int lane, const double (&x_eval)[E], double beta_oob) {
+    double *xe = L.XE + c * (DP + 2);
+#pragma unroll
+    for (int e = 0; e < E; ++e)
+        if (lane * E + e < DP) xe[lane * E + e] = x_eval[e];
+    if (lane == 0) {
+        xe[DP] = 1.;
+        xe[DP + 1] = 0.;
+        L.CH[c] = beta_oob;
+    }
+}
+
+// two row tiles against the same B operand, ACCUMULATED into acc0 / acc1 (the eight-chain 4 x 4 x 4 tiles of pld_tile2_q8).  The A
+// operands of a group of four k-steps are ST_IN doubles apart, groups st_out apart (one 16 x 16 block of PldDev::CS per group).
+template <int ST_IN>
+__device__ inline void pld_tile2_s8(const double *__restrict__ ap0, const double *__restrict__ ap1, const double *Bf, int n_steps, int lane,
+                                    PldAcc8 &acc0, PldAcc8 &acc1, size_t st_out) {
+    const double *bp = Bf + 8 * (lane >> 4) + (lane & 3);   // column n = lane & 3 of k = lane >> 4
+    const int n_g = n_steps >> 2;
+    double xa[4], ya[4], xb[4], yb[4];
+    auto fetch = [&](double (&x)[4], double (&y)[4], int g) {
+        const size_t o = (size_t)g * st_out;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { x[q] = ap0[o + q * ST_IN]; y[q] = ap1[o + q * ST_IN]; }
+    };
+    auto run = [&](int g, const double (&x)[4], const double (&y)[4]) {
+        double bl[4], bh[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { bl[q] = bp[(4 * g + q) * PLD_XS8]; bh[q] = bp[(4 * g + q) * PLD_XS8 + 4]; }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            acc0.lo = __builtin_amdgcn_mfma_f64_4x4x4f64(x[q], bl[q], acc0.lo, 0, 0, 0);
+            acc0.hi = __builtin_amdgcn_mfma_f64_4x4x4f64(x[q], bh[q], acc0.hi, 0, 0, 0);
+            acc1.lo = __builtin_amdgcn_mfma_f64_4x4x4f64(y[q], bl[q], acc1.lo, 0, 0, 0);
+            acc1.hi = __builtin_amdgcn_mfma_f64_4x4x4f64(y[q], bh[q], acc1.hi, 0, 0, 0);
+        }
+    };
+    if (n_g <= 0) return;
+    fetch(xa, ya, 0);
+    for (int g = 0; g < n_g; g += 2) {   // (the next group's A operands on their way while one runs)
+        if (g + 1 < n_g) fetch(xb, yb, g + 1);
+        run(g, xa, ya);
+        if (g + 1 < n_g) {
+            if (g + 2 < n_g) fetch(xa, ya, g + 2);
+            run(g + 1, xb, yb);
+        }
+    }
+}
+
+// Both passes, all eight waves of the workgroup (a workgroup-uniform call: it has barriers).  Before it every evaluating chain
+// wave has written its point (pld_s_point); after it RED holds the sums (pld_sums) and g[e] of an evaluating wave (J_0^T r) at
+// dimension lane E + e.  The last barrier precedes the gather of the last chunk: the caller's next writes to the block follow
+// a barrier of its own.
+template <int E>
+__device__ inline void pld_eval_stream_q8(const PldDev &pl, const PldLds &L, double alpha, int DP, int w, int nwv, int lane, bool evaluating,
+                                          double (&g)[E]) {
+    const int KC = pl.KC, NC = pl.NC, NT1 = pl.NT1, NKS = KC / 4;
+    const size_t half = (size_t)NKS * PLD_XS8, chunk_sz = (size_t)pl.MP * KC;
+    // ---- pass 1: F = C' Phi over the chunks ----
+    PldAcc8 F[PLD_S_TPW];
+#pragma unroll
+    for (int j = 0; j < PLD_S_TPW; ++j) F[j] = PldAcc8{0., 0.};
+    const double *xe = L.XE + w * (DP + 2);
+    const int off1 = ((lane & 15) >> 2) * 64 + (lane & 3) * 4 + (lane >> 4);   // A lane of GEMM1: o = 16 t + (lane & 15), p = 4 s + (lane >> 4)
+    for (int c = 0; c < NC; ++c) {
+        double *PB = L.PHI + (c & 1) * half;
+        if (evaluating)
+            for (int pl0 = lane; pl0 < KC; pl0 += 64) {
+                const unsigned mo = pl.mono[c * KC + pl0];
+                const double v = (xe[mo & 255u] * xe[(mo >> 8) & 255u]) * xe[(mo >> 16) & 255u];
+                PB[(pl0 >> 2) * PLD_XS8 + w + 8 * (pl0 & 3)] = v;
+            }
+        __syncthreads();
+        const double *CSc = pl.CS + c * chunk_sz + off1;
+#pragma unroll
+        for (int j = 0; j < PLD_S_TPW; j += 2) {
+            const int t0 = w + nwv * j, t1 = t0 + nwv;
+            if (t0 < NT1) {
+                if (t1 < NT1) {
+                    pld_tile2_s8<16>(CSc + (size_t)t0 * 16 * KC, CSc + (size_t)t1 * 16 * KC, PB, NKS, lane, F[j], F[j + 1], 256);
+                } else {
+                    PldAcc8 dup = F[j];
+                    pld_tile2_s8<16>(CSc + (size_t)t0 * 16 * KC, CSc + (size_t)t0 * 16 * KC, PB, NKS, lane, F[j], dup, 256);
+                }
+            }
+        }
+    }
+    {   // the epilogue of every tile of the wave, then its RED slot
+        const double inv_alpha = 1. / alpha;
+        const double beta[2] = {L.CH[lane & 3], L.CH[(lane & 3) + 4]};
+        double s_rr[2] = {0., 0.}, s_fr[2] = {0., 0.};
+#pragma unroll
+        for (int j = 0; j < PLD_S_TPW; ++j) {
+            const int t = w + nwv * j;
+            if (t < NT1) pld_epilogue1_q8(pl, L, alpha, inv_alpha, beta, t, F[j], lane, s_rr, s_fr);
+        }
+        pld_red_put_q8(L, w, lane, s_rr, s_fr);
+    }
+    __syncthreads();   // r complete in RB
+    // ---- pass 2: W rows of each chunk = C'^T r, then the gather ----
+#pragma unroll
+    for (int e = 0; e < E; ++e) g[e] = 0.;
+    const int off2 = ((lane & 15) >> 2) * 16 + (lane >> 4) * 4 + (lane & 3);   // A lane of GEMM2: p = 16 u + (lane & 15), o = 4 s + (lane >> 4)
+    const int NTC = KC / 16, i4 = lane >> 4, b4 = (lane >> 2) & 3, n4 = lane & 3;
+    for (int c = 0; c < NC; ++c) {
+        double *WB = L.PHI + (c & 1) * half;
+        const double *CSc = pl.CS + c * chunk_sz + off2;
+        for (int u = w; u < NTC; u += 2 * nwv) {
+            const int u2 = u + nwv < NTC ? u + nwv : u;
+            PldAcc8 a0 = {0., 0.}, a1 = {0., 0.};
+            pld_tile2_s8<64>(CSc + (size_t)u * 256, CSc + (size_t)u2 * 256, L.RB, pl.NS2, lane, a0, a1, (size_t)16 * KC);
+            double *W0 = WB + (size_t)(4 * u + b4) * PLD_XS8 + n4 + 8 * i4;   // monomial 16 u + 4 b + i of the chunk
+            W0[0] = a0.lo;
+            W0[4] = a0.hi;
+            if (u2 != u) {
+                double *W1 = WB + (size_t)(4 * u2 + b4) * PLD_XS8 + n4 + 8 * i4;
+                W1[0] = a1.lo;
+                W1[4] = a1.hi;
+            }
+        }
+        __syncthreads();
+        if (evaluating) {
+            const unsigned long long *gt = pl.gtabc + (size_t)c * pl.n_entc * DP;
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const int dim = lane * E + e;
+                if (dim >= DP) continue;
+                double gv = g[e];
+                for (int i = 0; i < pl.n_entc; ++i) {
+                    const unsigned long long en = gt[(size_t)i * DP + dim];
+                    const unsigned eh = (unsigned)(en >> 32);
+                    const int p = (int)(unsigned)en;
+                    const double wv = WB[(p >> 2) * PLD_XS8 + w + 8 * (p & 3)];
+                    const double mult = (double)((eh >> 16) & 255u);
+                    gv += (mult * wv) * (xe[eh & 255u] * xe[(eh >> 8) & 255u]);
+                }
+                g[e] = gv;
+            }
+        }
+    }
 }
 #endif  // BF_HOST_EMU

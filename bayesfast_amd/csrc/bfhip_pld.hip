@@ -100,7 +100,8 @@ extern "C" int bfhip_pipeline_upload(bfhip_ctx *ctx, const bfhip_pipeline_desc *
                 if (j < 0 || j >= d || k < 0 || k >= d || l < 0 || l >= d) return bf_set_error(BFHIP_ERR_ARG, "mask3 out of range");
                 add(j, k, l, [&](int o) { return pm.cubic3[(((size_t)o * pm.n3 + a) * pm.n3 + b) * pm.n3 + c]; });
             }
-    const int nf = (int)mono.size(), PP = roundup(nf, 16);
+    const int nf = (int)mono.size();
+    int PP = roundup(nf, 16);
     int MP = roundup(m, 16);
     if (PP >= 65536) return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_pipeline_upload: %d monomials", nf);
 
@@ -191,16 +192,8 @@ extern "C" int bfhip_pipeline_upload(bfhip_ctx *ctx, const bfhip_pipeline_desc *
         }
         Cw.swap(C2); yw.swap(y2); fmuw.swap(f2);
     }
-    const int NT1 = MP / 16, NS1 = PP / 4, NT2 = PP / 16, NS2 = MP / 4;
-
-    // ---- A fragments of C' and C'^T ----
-    std::vector<double> CF((size_t)NT1 * NS1 * 64), CTF((size_t)NT2 * NS2 * 64);
-    for (int t = 0; t < NT1; ++t)
-        for (int s = 0; s < NS1; ++s)
-            for (int l = 0; l < 64; ++l) CF[((size_t)t * NS1 + s) * 64 + l] = Cw[(size_t)(16 * t + (l & 15)) * PP + 4 * s + (l >> 4)];
-    for (int u = 0; u < NT2; ++u)
-        for (int s = 0; s < NS2; ++s)
-            for (int l = 0; l < 64; ++l) CTF[((size_t)u * NS2 + s) * 64 + l] = Cw[(size_t)(4 * s + (l >> 4)) * PP + 16 * u + (l & 15)];
+    const int NT1 = MP / 16, NS2 = MP / 4;
+    int NS1 = PP / 4, NT2 = PP / 16;
 
     // ---- monomial table and, per dimension, the monomials that contain it with their cofactors ----
     std::vector<unsigned> mono_tab(PP, (unsigned)ZERO | ((unsigned)ZERO << 8) | ((unsigned)ZERO << 16));
@@ -237,6 +230,7 @@ extern "C" int bfhip_pipeline_upload(bfhip_ctx *ctx, const bfhip_pipeline_desc *
     long best_cost = 0;
     // (the sixteen-chain forms' layout first -- every form can run then --, else the eight-chain forms' compact rows)
     for (int xs : {PLD_XS, PLD_XS8}) {
+        if (bf_tune().pld_stream == 1) break;
         for (int ks = 1; ks <= PLD_MAX_KS2; ++ks) {
             const int kpj = roundup((NS2 + ks - 1) / ks, 4);
             if (ks > 1 && (ks - 1) * kpj >= NS2) continue;   // an empty part
@@ -246,10 +240,67 @@ extern "C" int bfhip_pipeline_upload(bfhip_ctx *ctx, const bfhip_pipeline_desc *
         }
         if (best_ks) { only8 = xs == PLD_XS8; break; }
     }
-    if (!best_ks) {
-        dm.pld.on = 0;
-        return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_pipeline_upload: %d outputs x %d monomials need %zu KB of LDS per workgroup (160 KB)",
-                            m, nf, (base_bytes + pld_lds_doubles(DP, MP, PP, 1, (int)n_ent, PLD_XS8) * sizeof(double)) / 1024);
+    // ---- streamed form: where the resident block does not fit (or pld_stream = 1), the monomials in chunks of KC ----
+    const bool stream = !best_ks || bf_tune().pld_stream == 1;
+    int KC = 0, NC = 0;
+    size_t n_entc = 0;
+    if (stream) {
+        if (NT1 > 8 * PLD_S_TPW) {
+            dm.pld.on = 0;
+            return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_pipeline_upload: the streamed pipeline density holds min(outputs, monomials) <= %d "
+                                "(F row tiles in registers); this one has %d outputs x %d monomials -> %d rows", 128 * PLD_S_TPW, m, nf, m_eff);
+        }
+        for (int kc = 16; kc <= PP; kc += 16)   // (the largest chunk whose double buffer fits beside the sampler's own regions)
+            if (base_bytes + pld_s_lds_doubles(DP, MP, kc) * sizeof(double) <= (size_t)160 * 1024) KC = kc;
+        if (!KC) {
+            dm.pld.on = 0;
+            return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_pipeline_upload: %d outputs x %d monomials need %zu KB of LDS per workgroup even "
+                                "streamed in chunks of 16 monomials (160 KB)", m, nf, (base_bytes + pld_s_lds_doubles(DP, MP, 16) * sizeof(double)) / 1024);
+        }
+        NC = (PP + KC - 1) / KC;
+        // (the padding monomials of the last chunk are zeros: C' columns and table entries both)
+        const int PPS = NC * KC;
+        std::vector<double> C2((size_t)MP * PPS, 0.);
+        for (int i = 0; i < MP; ++i)
+            for (int p = 0; p < PP; ++p) C2[(size_t)i * PPS + p] = Cw[(size_t)i * PP + p];
+        Cw.swap(C2);
+        mono_tab.resize(PPS, (unsigned)ZERO | ((unsigned)ZERO << 8) | ((unsigned)ZERO << 16));
+        PP = PPS;
+        NS1 = PP / 4;
+        NT2 = PP / 16;
+        best_ks = 1;
+        only8 = 1;
+        // the gradient table per chunk: each dimension's entries in increasing p (as in gtab), p relative to the chunk
+        std::vector<size_t> cnt((size_t)NC * DP, 0);
+        for (int j = 0; j < DP; ++j)
+            for (unsigned long long en : per_dim[j]) ++cnt[(size_t)((unsigned)en / KC) * DP + j];
+        for (size_t v : cnt) n_entc = v > n_entc ? v : n_entc;
+        std::vector<unsigned long long> gt2((size_t)NC * n_entc * DP, pad_ent);
+        std::fill(cnt.begin(), cnt.end(), 0);
+        for (int j = 0; j < DP; ++j)
+            for (unsigned long long en : per_dim[j]) {
+                const unsigned p = (unsigned)en, c = p / KC;
+                const size_t i = cnt[(size_t)c * DP + j]++;
+                gt2[((size_t)c * n_entc + i) * DP + j] = (en & ~0xffffffffull) | (unsigned long long)(p % KC);
+            }
+        gtab.swap(gt2);
+    }
+
+    // ---- A fragments of C' and C'^T (resident form), or C' in the streamed form's blocks ----
+    std::vector<double> CF, CTF;
+    if (stream) {
+        CF.assign((size_t)MP * PP, 0.);
+        for (int i = 0; i < MP; ++i)
+            for (int p = 0; p < PP; ++p) CF[pld_cs_index(i, p, MP, KC)] = Cw[(size_t)i * PP + p];
+    } else {
+        CF.resize((size_t)NT1 * NS1 * 64);
+        CTF.resize((size_t)NT2 * NS2 * 64);
+        for (int t = 0; t < NT1; ++t)
+            for (int s = 0; s < NS1; ++s)
+                for (int l = 0; l < 64; ++l) CF[((size_t)t * NS1 + s) * 64 + l] = Cw[(size_t)(16 * t + (l & 15)) * PP + 4 * s + (l >> 4)];
+        for (int u = 0; u < NT2; ++u)
+            for (int s = 0; s < NS2; ++s)
+                for (int l = 0; l < 64; ++l) CTF[((size_t)u * NS2 + s) * 64 + l] = Cw[(size_t)(4 * s + (l >> 4)) * PP + 16 * u + (l & 15)];
     }
 
     // ---- one device buffer: doubles, then 8-byte entries, then the monomial words ----
@@ -273,7 +324,7 @@ extern "C" int bfhip_pipeline_upload(bfhip_ctx *ctx, const bfhip_pipeline_desc *
     double *hd = (double *)hb.data();
     size_t o = 0;
     const size_t o_cf = o; memcpy(hd + o, CF.data(), CF.size() * 8); o += CF.size();
-    const size_t o_ctf = o; memcpy(hd + o, CTF.data(), CTF.size() * 8); o += CTF.size();
+    const size_t o_ctf = o; if (!CTF.empty()) memcpy(hd + o, CTF.data(), CTF.size() * 8); o += CTF.size();
     const size_t o_y = o; memcpy(hd + o, yw.data(), (size_t)MP * 8); o += MP;
     const size_t o_f = o; memcpy(hd + o, fmuw.data(), (size_t)MP * 8); o += MP;
     const size_t o_pr = o; memcpy(hd + o, prior.data(), prior.size() * 8); o += prior.size();
@@ -288,13 +339,18 @@ extern "C" int bfhip_pipeline_upload(bfhip_ctx *ctx, const bfhip_pipeline_desc *
     pl.k_ff = k_ff; pl.k_fy = k_fy;
     pl.nf = nf; pl.PP = PP; pl.NS1 = NS1; pl.NT2 = NT2;
     pl.KS2 = best_ks; pl.KPJ2 = roundup((NS2 + best_ks - 1) / best_ks, 4);
-    pl.n_ent = (int)n_ent;
+    pl.n_ent = stream ? 0 : (int)n_ent;
     pl.only8 = only8;
     pl.has_prior = ds->prior_mu != NULL;
     pl.tri = compress ? 1 : 0;   // (the Householder factorisation left R: zero below the diagonal, exactly)
-    pl.CF = dbase + o_cf; pl.CTF = dbase + o_ctf; pl.yw = dbase + o_y; pl.fmuw = dbase + o_f;
+    pl.CF = stream ? NULL : dbase + o_cf; pl.CTF = stream ? NULL : dbase + o_ctf; pl.yw = dbase + o_y; pl.fmuw = dbase + o_f;
     pl.prior_mu = dbase + o_pr; pl.prior_prec = dbase + o_pr + DP;
-    pl.gtab = (const unsigned long long *)(dbase + o_g);
+    pl.gtab = stream ? NULL : (const unsigned long long *)(dbase + o_g);
+    pl.stream = stream ? 1 : 0;
+    pl.KC = KC; pl.NC = NC;
+    pl.n_entc = (int)n_entc;
+    pl.CS = stream ? dbase + o_cf : NULL;
+    pl.gtabc = stream ? (const unsigned long long *)(dbase + o_g) : NULL;
     pl.mono = (const unsigned *)(dbase + o_m);
     pl.logp0 = ds->logp0 - 0.5 * k_yy;   // (the part of the data vector outside the surrogate's column space: a constant)
     pl.prior_c0 = ds->prior_c0;
@@ -318,17 +374,21 @@ __device__ inline double pld_frag_at(const double *Mf, int DP, int i, int k) {
 }
 
 // NPT points per workgroup: 16 (sixteen waves, 16-column tiles) or 8 (eight waves, the eight-chain forms' compact LDS rows: what
-// a surrogate with more monomials than the sixteen-point layout holds runs on); E dimensions per lane (2 at d > 64)
-template <int NPT, int E>
+// a surrogate with more monomials than the sixteen-point layout holds runs on); E dimensions per lane (2 at d > 64); STREAM (NPT = 8):
+// the streamed form (PldDev::stream, pld_eval_stream_q8)
+template <int NPT, int E, bool STREAM = false>
 __global__ __launch_bounds__(NPT * 64) void bf_pld_logp_grad_kernel(DevModel m, int n, const double *__restrict__ x, int original_space,
                                                                   double *__restrict__ logp, double *__restrict__ grad) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const PldDev &pl = m.pld;
     const int DP = m.DP, d = m.d;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const PldLds L = pld_lds(lds, DP, pl, NPT);
-    double *XM = lds + pld_lds_doubles(DP, pl.MP, pl.PP, pl.KS2, pl.n_ent, L.XS);   // [NPT][2][DP]  x - mu and x_o - mu_decay of every point
-    pld_stage(pl, L, DP, tid, NPT * 64);
+    static_assert(!STREAM || NPT == 8, "the streamed form has eight chains");
+    const PldLds L = STREAM ? pld_s_lds(lds, DP, pl) : pld_lds(lds, DP, pl, NPT);
+    // [NPT][2][DP]  x - mu and x_o - mu_decay of every point
+    double *XM = lds + (STREAM ? pld_s_lds_doubles(DP, pl.MP, pl.KC) : pld_lds_doubles(DP, pl.MP, pl.PP, pl.KS2, pl.n_ent, L.XS));
+    if constexpr (STREAM) pld_s_stage(pl, L, tid, NPT * 64);
+    else pld_stage(pl, L, DP, tid, NPT * 64);
     const bool tr = m.has_transform && !original_space;
     for (int base = blockIdx.x * NPT; base < n; base += gridDim.x * NPT) {
         const int i = base + w;
@@ -387,14 +447,21 @@ __global__ __launch_bounds__(NPT * 64) void bf_pld_logp_grad_kernel(DevModel m, 
             const double xv = beta > 0. ? (m.alpha * xs[e] + (beta - m.alpha) * mu[e]) / beta : xs[e];   // :482
             x_eval[e] = (valid && on[e]) ? xv : 0.;
         }
-        pld_point_e<E>(pl, L, DP, w, lane, x_eval, valid ? beta : 0.);
-        __syncthreads();
-        if constexpr (NPT == 8) pld_gemm1_q8(pl, L, m.alpha, w, 8, lane);
-        else pld_gemm1(pl, L, m.alpha, w, 16, lane);
-        __syncthreads();
-        if constexpr (NPT == 8) pld_gemm2_q8(pl, L, w, 8, lane);
-        else pld_gemm2(pl, L, w, 16, lane);
-        __syncthreads();
+        double gs[E];   // (the streamed form: J_0^T r, gathered chunk by chunk)
+        if constexpr (STREAM) {
+            pld_s_point<E>(L, DP, w, lane, x_eval, valid ? beta : 0.);
+            pld_eval_stream_q8<E>(pl, L, m.alpha, DP, w, 8, lane, true, gs);
+        } else {
+            (void)gs;
+            pld_point_e<E>(pl, L, DP, w, lane, x_eval, valid ? beta : 0.);
+            __syncthreads();
+            if constexpr (NPT == 8) pld_gemm1_q8(pl, L, m.alpha, w, 8, lane);
+            else pld_gemm1(pl, L, m.alpha, w, 16, lane);
+            __syncthreads();
+            if constexpr (NPT == 8) pld_gemm2_q8(pl, L, w, 8, lane);
+            else pld_gemm2(pl, L, w, 16, lane);
+            __syncthreads();
+        }
         double s_rr, s_fr;
         pld_sums(pl, L, w, lane, NPT, s_rr, s_fr);
         s_rr = pld_wave_sum(s_rr);
@@ -402,7 +469,8 @@ __global__ __launch_bounds__(NPT * 64) void bf_pld_logp_grad_kernel(DevModel m, 
         double gn[E], dj = 0.;
 #pragma unroll
         for (int e = 0; e < E; ++e) {
-            gn[e] = lane * E + e < DP ? pld_grad(pl, L, DP, w, lane * E + e) : 0.;   // (J_0^T r)_dim
+            if constexpr (STREAM) gn[e] = lane * E + e < DP ? gs[e] : 0.;
+            else gn[e] = lane * E + e < DP ? pld_grad(pl, L, DP, w, lane * E + e) : 0.;   // (J_0^T r)_dim
             dj += gn[e] * xm[e];
         }
         if (beta > 0.) {   // (compressed outputs: the tails of Q^T f_mu' and Q^T y' as scalars, bfhip_pipeline_upload)
@@ -452,6 +520,19 @@ __global__ __launch_bounds__(NPT * 64) void bf_pld_logp_grad_kernel(DevModel m, 
 
 int bf_pld_logp_grad(bfhip_ctx *ctx, int n, const double *x, int original_space, double *logp, double *grad) {
     const DevModel &m = ctx->model;
+    if (m.pld.stream) {   // the streamed form: eight points per workgroup
+        const size_t lds = (pld_s_lds_doubles(m.DP, m.pld.MP, m.pld.KC) + (size_t)8 * 2 * m.DP) * sizeof(double);
+        if (lds > (size_t)160 * 1024) return bf_set_error(BFHIP_ERR_UNSUPPORTED, "pipeline density: %zu KB of LDS", lds / 1024);
+        const bool e2 = m.DP > 64;
+        void (*k)(DevModel, int, const double *, int, double *, double *) = e2 ? bf_pld_logp_grad_kernel<8, 2, true> : bf_pld_logp_grad_kernel<8, 1, true>;
+        if (lds > 64 * 1024) BF_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        snprintf(bf_tune().last_kernel, sizeof(bf_tune().last_kernel), "bf_pld_logp_grad_kernel<8, %d, true>", e2 ? 2 : 1);
+        int grid = (n + 7) / 8;
+        if (grid > 4 * ctx->n_cu) grid = 4 * ctx->n_cu;
+        hipLaunchKernelGGL(k, dim3(grid), dim3(8 * 64), lds, ctx->stream, m, n, x, original_space, logp, grad);
+        BF_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     const int npt = m.pld.only8 ? 8 : 16;
     const size_t lds = (pld_lds_doubles(m.DP, m.pld.MP, m.pld.PP, m.pld.KS2, m.pld.n_ent, npt == 8 ? PLD_XS8 : PLD_XS) + (size_t)npt * 2 * m.DP) * sizeof(double);
     if (lds > (size_t)160 * 1024) return bf_set_error(BFHIP_ERR_UNSUPPORTED, "pipeline density: %zu KB of LDS", lds / 1024);

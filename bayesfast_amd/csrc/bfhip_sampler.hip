@@ -95,7 +95,7 @@ struct SamplerGeo {
 // one from the first read of its result)
 #define BF_MFMA_Q_ACC(acc, af, xv) asm volatile("s_nop 1\n\tv_mfma_f64_4x4x4_4b_f64 %0, %1, %2, %0" : "+v"(acc) : "a"(af), "v"(xv))
 #define BF_MFMA_Q_DONE(a0, a1, a2, a3) asm volatile("s_nop 7\n\ts_nop 7" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3))
-#define BF_SAMPLER_WAVES(W, FULLM, FS) ((FS) == 17 ? 4 : (((W) == 8 || (FULLM) || (FS) == 9 || (FS) == 10) ? 8 : 16))
+#define BF_SAMPLER_WAVES(W, FULLM, FS) ((FS) == 17 ? 4 : (((W) == 8 || (FULLM) || (FS) == 9 || (FS) == 10 || (FS) == 11) ? 8 : 16))
 
 // PLAIN fixes the feature set of the common surrogate at compile time (linear + quadratic configs with the
 // extrapolation bound; no constraint transform, no input scaling, no decay, no cubic configs): the branches
@@ -113,9 +113,10 @@ __global__ __launch_bounds__(BF_SAMPLER_WAVES(W, FULLM, FS) * 64) void bf_sample
     constexpr int NWV = BF_SAMPLER_WAVES(W, FULLM, FS), NTH = NWV * 64;  // waves (= chains) of a workgroup, threads
     // FS == 8: the pipeline density (bfhip_pld.h: multi-output surrogate + Gaussian likelihood + prior); transforms, input
     // scaling, bound and decay are run-time features as in FS == 0, the polynomial itself is the two contractions of phase P
-    constexpr bool PLD = FS == 8 || FS == 9 || FS == 10;   // (9: eight waves of 256 registers, for launches of at most 8 chains per CU;
-    constexpr bool PLDC = FS == 10;                         //  10: the same with the DES-shaped feature set fixed at compile time -- box
-                                                            //  transform, input scaling, bound, no decay term)
+    constexpr bool PLD = FS == 8 || FS == 9 || FS == 10 || FS == 11;   // (9: eight waves of 256 registers, for launches of at most 8 chains
+    constexpr bool PLDC = FS == 10;                         //  per CU; 10: the same with the DES-shaped feature set fixed at compile time -- box
+                                                            //  transform, input scaling, bound, no decay term; 11: the streamed form,
+    constexpr bool PLDS = FS == 11;                         //  eight waves, run-time feature set: bfhip_pld.h, pld_eval_stream_q8)
 #ifndef BF_CHAIN_UNITS_MORE
 #define BF_CHAIN_UNITS_MORE 0
 #endif
@@ -211,7 +212,10 @@ __global__ __launch_bounds__(BF_SAMPLER_WAVES(W, FULLM, FS) * 64) void bf_sample
     double *CUB = GB + (((size_t)a.gbn * 16 * GS + 1) & ~(size_t)1);  // [n2 n2] A2t | [n2 n2] A2 | [nc3 n3 n3 16] T3x
     // pipeline density: its regions behind the matvec results (there are no cubic tables then)
     PldLds PL;
-    if constexpr (PLD) {
+    if constexpr (PLDS) {
+        PL = pld_s_lds(CUB, DP, m.pld);
+        pld_s_stage(m.pld, PL, tid, NTH);
+    } else if constexpr (PLD) {
         PL = pld_lds(CUB, DP, m.pld, NWV == 8 ? 8 : 16, NWV == 8 && a.pld_cl != 0);   // (the eight-chain forms: compact B-operand rows)
         pld_stage(m.pld, PL, DP, tid, NTH);
     }
@@ -1444,9 +1448,14 @@ __global__ __launch_bounds__(BF_SAMPLER_WAVES(W, FULLM, FS) * 64) void bf_sample
                     const double xv = beta_o > 0. ? (m.alpha * xs[e] + (beta_o - m.alpha) * c_mu[e]) / beta_o : xs[e];   // :482
                     x_ev[e] = lane * E + e < d ? xv : 0.;
                 }
-                pld_point_e<E>(pl, PL, DP, w, lane, x_ev, beta_o);
+                if constexpr (PLDS) pld_s_point<E>(PL, DP, w, lane, x_ev, beta_o);
+                else pld_point_e<E>(pl, PL, DP, w, lane, x_ev, beta_o);
             }
-            if (pld_eval) {   // (uniform over the workgroup)
+            double gst[E];   // (the streamed form: J_0^T r, gathered chunk by chunk)
+            (void)gst;
+            if constexpr (PLDS) {
+                if (pld_eval) pld_eval_stream_q8<E>(pl, PL, m.alpha, DP, w, NWV, lane, evaluating, gst);   // (uniform over the workgroup)
+            } else if (pld_eval) {   // (uniform over the workgroup)
             TRACEP(7);
             __syncthreads();  // P1: monomials of every evaluating chain
             TRACEP(8);
@@ -1468,7 +1477,8 @@ __global__ __launch_bounds__(BF_SAMPLER_WAVES(W, FULLM, FS) * 64) void bf_sample
                 double gj0[E], dj = 0.;
 #pragma unroll
                 for (int e = 0; e < E; ++e) {
-                    gj0[e] = lane * E + e < DP ? pld_grad(pl, PL, DP, w, lane * E + e) : 0.;   // (J_0^T r)_dim
+                    if constexpr (PLDS) gj0[e] = lane * E + e < DP ? gst[e] : 0.;
+                    else gj0[e] = lane * E + e < DP ? pld_grad(pl, PL, DP, w, lane * E + e) : 0.;   // (J_0^T r)_dim
                     dj += gj0[e] * xmv[e];
                 }
                 if (beta_o > 0.) {   // (compressed outputs: the tails of Q^T f_mu' and Q^T y' as scalars, bfhip_pipeline_upload)
@@ -1846,6 +1856,8 @@ static bool sampler_cubic_lds(const DevModel &m, bool plain) {
            (sampler_lds_base(m, plain) + sampler_cubic_doubles(m)) * sizeof(double) <= (size_t)160 * 1024;
 }
 static size_t sampler_lds_bytes(const DevModel &m, bool plain, int nwv = 16) {
+    if (m.pld.on && m.pld.stream)   // (the streamed form's block, at the same place)
+        return (((sampler_lds_base(m, false) + 1) & ~(size_t)1) + pld_s_lds_doubles(m.DP, m.pld.MP, m.pld.KC)) * sizeof(double);
     if (m.pld.on)   // (the pipeline block sits where the cubic tables would: behind the matvec results, 16-byte aligned)
         return (((sampler_lds_base(m, false) + 1) & ~(size_t)1) +
                 pld_lds_doubles(m.DP, m.pld.MP, m.pld.PP, m.pld.KS2, m.pld.n_ent, nwv == 8 ? PLD_XS8 : PLD_XS)) * sizeof(double);
@@ -1874,7 +1886,7 @@ static int launch_sampler_t(bfhip_ctx *ctx, const SamplerArgs &args_in) {
     size_t lds = sampler_lds_bytes(ctx->model, FS == 1, NWV);
     SamplerArgs args = args_in;
     args.pld_cl = 0;
-    if (ctx->model.pld.on && NWV == 8 && !(bf_tune().pld_no_cl != 0)) {
+    if (ctx->model.pld.on && !ctx->model.pld.stream && NWV == 8 && !(bf_tune().pld_no_cl != 0)) {
         // the eight-wave forms read the A operands of both contractions from a row-major copy of C' in LDS when it fits behind the
         // rest (the DES shape: 52 KB), instead of streaming 2 x 51 KB of fragments from L2 in every trip -- the same numbers
         const size_t with_cl = lds + pld_cl_doubles(ctx->model.pld.MP, ctx->model.pld.PP) * sizeof(double) + 16;
@@ -2079,6 +2091,12 @@ template <int W, bool NUTS>
 static int launch_sampler(bfhip_ctx *ctx, const SamplerArgs &args) {
     const DevModel &m = ctx->model;
     const bool plain = sampler_plain(m) && !args.mat;
+    if (m.pld.on && m.pld.stream) {   // the streamed pipeline density: FS = 11, eight waves, either metric
+        if (sampler_lds_bytes(m, false, 8) > (size_t)160 * 1024)
+            return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_sampler_run: this streamed pipeline density needs %zu KB of LDS at d = %d (160 KB)",
+                                sampler_lds_bytes(m, false, 8) / 1024, m.d);
+        return args.mat ? launch_sampler_t<W, NUTS, false, 11, 1>(ctx, args) : launch_sampler_t<W, NUTS, false, 11>(ctx, args);
+    }
     if (m.pld.on) {   // pipeline density: the FS = 8 / 9 / 10 instantiations
         if constexpr (W == 8) {
             // d = 128 (round 6): the eight-wave form with the run-time feature set, two dimensions per lane in phase P

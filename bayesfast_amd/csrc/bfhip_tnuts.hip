@@ -499,6 +499,9 @@ extern "C" int bfhip_tnuts_run(bfhip_ctx *ctx, const bfhip_sampler_config *cfg, 
         return bf_set_error(BFHIP_ERR_ARG, "bfhip_tnuts_run: invalid sampler configuration");
     if (cfg->full_metric && !cfg->metric_mat) return bf_set_error(BFHIP_ERR_ARG, "bfhip_tnuts_run: full_metric needs metric_mat");
     const DevModel &m = ctx->model;
+    if (m.pld.on && m.pld.stream)
+        return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_tnuts_run: tempered NUTS does not run the streamed form of the pipeline density "
+                            "(%d monomials in %d chunks)", m.pld.nf, m.pld.NC);
     // the tuned instantiations: the common surrogate (linear + quadratic configs with the bound; constraint transform and decay
     // optional) at d <= 64 with the diagonal metric.  Everything else -- cubic configs, d = 128, device-side input scaling, the
     // Gaussian link, the pipeline density, the full-rank metric -- runs on the generic kernel (bfhip_tnuts_gen.hip)

@@ -30,6 +30,7 @@ struct BfTune {
     int no_decay_shared; // BFHIP_NO_DECAY_SHARED: the pipelined kernel runs the decay term's third matrix also when it is the bound's (tests compare)
     int pld_no_cl;       // BFHIP_PLD_NO_CL: the pipeline density's contractions stream their A fragments from L2 also where the LDS copy fits (tests compare)
     int pld_no_compress; // BFHIP_PLD_NO_COMPRESS: the pipeline density without the output-space compression (read at upload)
+    int pld_stream;      // BFHIP_PLD_STREAM: 1 = the pipeline density's streamed form also where the resident one fits (read at upload; tests compare)
     // --- measurement buffers (device pointers or NULL) ---
     unsigned long long *stamps, *stamps_lone, *gstamps, *group_counters;
     char last_kernel[96];

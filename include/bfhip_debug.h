@@ -13,7 +13,7 @@ extern "C" {
 #endif
 
 /* Integer switches by name: "no_group", "no_pipe", "no_plain", "no_quad", "wave_cpg", "tail_relaunch", "tail_stop", "tail_q",
- * "tail_max", "lone", "lone_form", "pld_waves", "cubic_form", "cubic_loops", "gram_one_wave", "chol_one_panel", "no_vel_ahead", "tnuts_wpb", "tnuts_generic", "no_bound_proof", "no_proof_weights", "pld_no_compress", "pld_no_cl", "polar_tiles", "no_decay_shared", "no_group_pld".
+ * "tail_max", "lone", "lone_form", "pld_waves", "cubic_form", "cubic_loops", "gram_one_wave", "chol_one_panel", "no_vel_ahead", "tnuts_wpb", "tnuts_generic", "no_bound_proof", "no_proof_weights", "pld_no_compress", "pld_stream", "pld_no_cl", "polar_tiles", "no_decay_shared", "no_group_pld".
  * Returns 0, or BFHIP_ERR_ARG for an unknown key. */
 int bfhip_debug_set(const char *key, long long value);
 /* The current value of a switch (0 for an unknown key). */
