@@ -149,13 +149,7 @@ extern "C" int bfhip_density_upload(bfhip_ctx *ctx, const bfhip_density_desc *ds
     const size_t MAT = (size_t)DP * DP, n_dbl = h.size();
     BF_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t bytes = n_dbl * sizeof(double);
-    if (ctx->model_bytes < bytes) {
-        if (ctx->model_buf) BF_HIP_CHECK(hipFree(ctx->model_buf));
-        ctx->model_buf = NULL;
-        ctx->model_bytes = 0;
-        BF_HIP_CHECK(hipMalloc(&ctx->model_buf, bytes));
-        ctx->model_bytes = bytes;
-    }
+    if (int rc = bf_grow(ctx, &ctx->model_buf, &ctx->model_bytes, bytes)) return rc;
     BF_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // nobody may still read the old model
     BF_HIP_CHECK(hipMemcpy(ctx->model_buf, h.data(), bytes, hipMemcpyHostToDevice));
     DevModel &m = ctx->model;
@@ -230,13 +224,7 @@ extern "C" int bfhip_density_upload(bfhip_ctx *ctx, const bfhip_density_desc *ds
                 }
         const size_t ib = (size_t)(n2 + n3 + 2 * DP) * sizeof(int), ibp = (ib + 7) / 8 * 8;
         const size_t cbytes = ibp + (A2.size() * 2 + T3.size()) * sizeof(double) + 8;
-        if (ctx->cubic_bytes < cbytes) {
-            if (ctx->cubic_buf) BF_HIP_CHECK(hipFree(ctx->cubic_buf));
-            ctx->cubic_buf = NULL;
-            ctx->cubic_bytes = 0;
-            BF_HIP_CHECK(hipMalloc(&ctx->cubic_buf, cbytes));
-            ctx->cubic_bytes = cbytes;
-        }
+        if (int rc = bf_grow(ctx, &ctx->cubic_buf, &ctx->cubic_bytes, cbytes)) return rc;
         std::vector<char> hb(cbytes, 0);
         int *ip = (int *)hb.data();
         memcpy(ip, mask2.data(), n2 * sizeof(int));

@@ -55,12 +55,12 @@ struct bfhip_ctx {
         const double *A2, *A2t, *T3t;
     } pm;
     int *tail_buf;        // the chains of a launch's tail: count, then their indices (bfhip_sampler.hip: launch_nuts_pipe)
-    int tail_cap;
+    size_t tail_bytes;
     void *scratch;        // sampler tree scratch (grow-only)
     size_t scratch_bytes;
     int n_cu;
     void *flow;           // counters and exchange buffers of the triangular solves (bfhip_fit.hip: ensure_flow)
-    int flow_cap;         // in 64-row blocks
+    size_t flow_bytes;
 };
 
 // Every entry point that launches or allocates runs on its context's device, whatever the caller's current device is
@@ -74,7 +74,38 @@ struct BfDeviceGuard {
     ~BfDeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-// the common surrogate: linear + quadratic configs with the extrapolation bound and nothing else
-static inline bool bf_model_plain(const DevModel &m) {
-    return m.has_quad && m.use_bound && !m.use_decay && !m.has_transform && !m.has_su && !m.has_cubic && !m.has_link;
+// ---- host-side launch plumbing ----------------------------------------------------------------------
+#define BF_LDS_MAX ((size_t)160 * 1024)   // dynamic LDS of one workgroup on gfx950
+
+// Opts a kernel into more than 64 KB of dynamic LDS.  The attribute belongs to the kernel on the current device, so it is raised
+// at every call rather than remembered (one process may drive several GPUs).
+template <typename K>
+static inline int bf_set_lds(K kern, size_t bytes) {
+    if (bytes > 64 * 1024)
+        BF_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return 0;
+}
+
+// Grow-only device buffer: at least need bytes at *buf, *bytes its size.  Growing waits for the context's stream (nothing
+// may still use the old buffer); allocation is outside any timed region after the first call.
+static inline int bf_grow(bfhip_ctx *ctx, void **buf, size_t *bytes, size_t need) {
+    if (*bytes >= need) return 0;
+    BF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (*buf) BF_HIP_CHECK(hipFree(*buf));
+    *buf = NULL;
+    *bytes = 0;
+    BF_HIP_CHECK(hipMalloc(buf, need));
+    *bytes = need;
+    return 0;
+}
+
+// the common surrogate: linear + quadratic configs with the extrapolation bound; decay term and constraint transform optional
+static inline bool bf_common_surrogate(const DevModel &m) {
+    return m.has_quad && m.use_bound && !m.has_su && !m.has_cubic && !m.has_link;
+}
+// ... with neither of the optional terms
+static inline bool bf_model_plain(const DevModel &m) { return bf_common_surrogate(m) && !m.use_decay && !m.has_transform; }
+// the feature-set bits of the compile-time instantiations: 1 | decay << 1 | transform << 2 (the pipeline density: 8 | transform << 2)
+static inline int bf_feature_bits(const DevModel &m) {
+    return m.pld.on ? (8 | (m.has_transform ? 4 : 0)) : (1 | (m.use_decay ? 2 : 0) | (m.has_transform ? 4 : 0));
 }

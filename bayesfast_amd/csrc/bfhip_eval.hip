@@ -334,13 +334,6 @@ __global__ __launch_bounds__(256) void bf_leapfrog_kernel(DevModel m, int stage_
     }
 }
 
-template <typename K>
-static int bf_set_lds(K kern, size_t bytes) {
-    if (bytes > 64 * 1024)
-        BF_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return 0;
-}
-
 template <int T, bool STAGE>
 static int launch_logp_grad(bfhip_ctx *ctx, int grid, size_t lds, int n, const double *x, int original_space,
                             double *logp, double *grad) {

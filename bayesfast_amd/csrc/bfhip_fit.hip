@@ -328,18 +328,6 @@ __global__ void bf_atb_reduce_kernel(int P, int m, const double *__restrict__ pa
     r[(size_t)j * m + c] = s;
 }
 
-static int ensure_scratch(bfhip_ctx *ctx, size_t need) {
-    if (ctx->scratch_bytes < need) {
-        BF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (ctx->scratch) BF_HIP_CHECK(hipFree(ctx->scratch));
-        ctx->scratch = NULL;
-        ctx->scratch_bytes = 0;
-        BF_HIP_CHECK(hipMalloc(&ctx->scratch, need));
-        ctx->scratch_bytes = need;
-    }
-    return 0;
-}
-
 extern "C" int bfhip_gram(bfhip_ctx *ctx, int n, int P, int m, const double *A, int lda, const double *B, double *G, double *r) {
     BfDeviceGuard dev_guard(ctx);
     if (!ctx || n < 1 || P < 1 || m < 0 || !A || !G || lda < P || (m > 0 && (!B || !r)))
@@ -363,13 +351,13 @@ extern "C" int bfhip_gram(bfhip_ctx *ctx, int n, int P, int m, const double *A, 
     size_t need = (size_t)split * n_blk * GB_ * GB_ * sizeof(double);
     const size_t need_atb = (size_t)ATB_SEG_ * (m > 0 ? m : 1) * P * sizeof(double);
     if (need < need_atb) need = need_atb;
-    if (int rc = ensure_scratch(ctx, need)) return rc;
+    if (int rc = bf_grow(ctx, &ctx->scratch, &ctx->scratch_bytes, need)) return rc;
     double *part = (double *)ctx->scratch;
     const int waves = n_blk * split;
     if (nb >= 8 && !bf_tune().gram_one_wave) {   // (below, the 64 x 64 blocks of a small Gram matrix fill the chip better one wave each)
         const int nb2 = (nb + 1) / 2;
         const size_t lds = (size_t)2 * G2_R * G2_LD * sizeof(double);
-        BF_HIP_CHECK(hipFuncSetAttribute((const void *)bf_gram128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (int rc = bf_set_lds(bf_gram128_kernel, lds)) return rc;
         hipLaunchKernelGGL(bf_gram128_kernel, dim3(nb2 * (nb2 + 1) / 2 * split), dim3(256), lds, ctx->stream, n, P, A, lda, nb, split, part);
     } else
     hipLaunchKernelGGL(bf_gram_kernel, dim3((waves + 3) / 4), dim3(256), 0, ctx->stream, n, P, A, lda, nb, split, part);
@@ -785,20 +773,17 @@ __global__ __launch_bounds__(256) void bf_trsv_flow_kernel(int P, int m, int q0,
     }
 }
 
+// [2 ints of counters, padded to 64 bytes][forward exchange buffer][backward exchange buffer], each exchange buffer n_x doubles
+static size_t flow_size(size_t n_x) { return 64 + 2 * n_x * sizeof(double); }
+static size_t flow_n_x(const bfhip_ctx *ctx) { return (ctx->flow_bytes - 64) / (2 * sizeof(double)); }
+
 static int ensure_flow(bfhip_ctx *ctx, int nb) {
-    if (ctx->flow_cap < nb) {
-        BF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (ctx->flow) BF_HIP_CHECK(hipFree(ctx->flow));
-        ctx->flow = NULL;
-        ctx->flow_cap = 0;
-        const int cap = nb < 256 ? 256 : 2 * nb;
-        // [2 ints of counters, padded to 64 bytes][forward exchange buffer][backward exchange buffer]
-        const size_t n_x = (size_t)cap * TRSV_MQ_ * NB_;
-        BF_HIP_CHECK(hipMalloc((void **)&ctx->flow, 64 + 2 * n_x * sizeof(double)));
-        BF_HIP_CHECK(hipMemsetAsync(ctx->flow, 0, 64, ctx->stream));
-        BF_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)((char *)ctx->flow + 64), 0x7FF8DEAD, 4 * n_x, ctx->stream));
-        ctx->flow_cap = cap;
-    }
+    if (ctx->flow_bytes >= flow_size((size_t)nb * TRSV_MQ_ * NB_)) return 0;
+    const int cap = nb < 256 ? 256 : 2 * nb;
+    const size_t n_x = (size_t)cap * TRSV_MQ_ * NB_;
+    if (int rc = bf_grow(ctx, &ctx->flow, &ctx->flow_bytes, flow_size(n_x))) return rc;
+    BF_HIP_CHECK(hipMemsetAsync(ctx->flow, 0, 64, ctx->stream));
+    BF_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)((char *)ctx->flow + 64), 0x7FF8DEAD, 4 * n_x, ctx->stream));
     return 0;
 }
 
@@ -811,7 +796,7 @@ static int chol_apply(bfhip_ctx *ctx, int P, int m, const double *L, const doubl
     const int nb = (P + NB_ - 1) / NB_;
     if (int rc = ensure_flow(ctx, nb)) return rc;
     int *sync = (int *)ctx->flow;
-    double *xf = (double *)((char *)ctx->flow + 64), *xb = xf + (size_t)ctx->flow_cap * TRSV_MQ_ * NB_;
+    double *xf = (double *)((char *)ctx->flow + 64), *xb = xf + flow_n_x(ctx);
     for (int q0 = 0; q0 < m; q0 += TRSV_MQ_) {
         const int mq = m - q0 < TRSV_MQ_ ? m - q0 : TRSV_MQ_;
         hipLaunchKernelGGL(bf_trsv_flow_kernel<false>, dim3(nb), dim3(256), 0, st, P, m, q0, mq, L, LinvAll, dsc, scale_in ? 1 : 0, r,
@@ -826,7 +811,7 @@ extern "C" int bfhip_solve_spd(bfhip_ctx *ctx, int P, int m, double *G, double *
     BfDeviceGuard dev_guard(ctx);
     if (!ctx || P < 1 || m < 1 || !G || !r || !info) return bf_set_error(BFHIP_ERR_ARG, "bfhip_solve_spd: invalid argument");
     const size_t n_inv = (size_t)((P + NB_ - 1) / NB_) * NB_ * NB_;
-    if (int rc = ensure_scratch(ctx, ((size_t)P + n_inv) * sizeof(double))) return rc;
+    if (int rc = bf_grow(ctx, &ctx->scratch, &ctx->scratch_bytes, ((size_t)P + n_inv) * sizeof(double))) return rc;
     double *dsc = (double *)ctx->scratch, *LinvAll = dsc + P;
     if (int rc = solve_spd_impl(ctx, P, m, G, r, info, dsc, LinvAll)) return rc;
     if (int rc = chol_apply(ctx, P, m, G, dsc, LinvAll, r, false)) return rc;
@@ -868,7 +853,7 @@ extern "C" int bfhip_lstsq(bfhip_ctx *ctx, int n, int P, int m, const double *A,
     if (int rc = bfhip_gram(ctx, n, P, m, A, lda, B, G, c)) return rc;
     // (the Gram scratch is free again; the scales and the block inverse live behind the A^T S partials of the refinement)
     const size_t n_atb = (size_t)ATB_SEG_ * m * P, n_inv = (size_t)((P + NB_ - 1) / NB_) * NB_ * NB_;
-    if (int rc = ensure_scratch(ctx, (n_atb + P + n_inv) * sizeof(double))) return rc;
+    if (int rc = bf_grow(ctx, &ctx->scratch, &ctx->scratch_bytes, (n_atb + P + n_inv) * sizeof(double))) return rc;
     double *part = (double *)ctx->scratch, *dsc = part + n_atb, *LinvAll = dsc + P;
     if (int rc = solve_spd_impl(ctx, P, m, G, c, info, dsc, LinvAll)) return rc;
     if (int rc = chol_apply(ctx, P, m, G, dsc, LinvAll, c, false)) return rc;

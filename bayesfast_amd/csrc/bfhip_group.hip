@@ -5,9 +5,6 @@
 #include "bfhip_group.h"
 #include "bfhip_split.h"
 
-// measurement hook (not part of include/bfhip.h): device buffer of two counters, trips and trips with the bound's tiles
-static unsigned long long *g_gcount_ptr() { return bf_tune().group_counters; }
-static unsigned long long *g_gstamps_ptr() { return bf_tune().gstamps; }
 int bf_no_bound_proof() { return bf_tune().no_bound_proof; }
 
 template <int W, bool NUTS, int FS>
@@ -25,8 +22,7 @@ static int launch_t(bfhip_ctx *ctx, const SamplerArgs &args) {
         lds = (((GroupGeo<W>::lds_doubles(((FS & 2) ? 3 : 2) - 1) + 1) & ~(size_t)1) + pld_lds_doubles(16 * W, pl.MP, pl.PP, 1, pl.n_ent, PLD_XS, W) +
                pld_cl_doubles(pl.MP, pl.PP) + 2) * sizeof(double);
     }
-    if (lds > 64 * 1024)
-        BF_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int rc = bf_set_lds(k, lds)) return rc;
     const int groups = (args.n_chain + 15) / 16;
     hipLaunchKernelGGL(k, dim3(groups), dim3(64 * W), lds, ctx->stream, ctx->model, args);
     BF_HIP_CHECK(hipGetLastError());
@@ -36,7 +32,7 @@ static int launch_t(bfhip_ctx *ctx, const SamplerArgs &args) {
 template <int W>
 static int launch_w(bfhip_ctx *ctx, const SamplerArgs &args, bool nuts, int fs) {
 #ifdef BF_ONLY_HEADLINE  // tuning builds (tools/gvariant.sh): the 64-d plain NUTS instantiation only
-    if (W == 4 && nuts && fs == 1) return launch_t<(W == 4 ? 4 : W), true, 1>(ctx, args);
+    if (nuts && fs == 1) return launch_t<W, true, 1>(ctx, args);
     return bf_set_error(BFHIP_ERR_UNSUPPORTED, "tuning build: headline instantiation only");
 #else
     if (nuts) {
@@ -72,36 +68,29 @@ bool bf_split_supports(const DevModel &m, const SamplerArgs &args) {
 #ifdef BF_ONLY_HEADLINE
     if (m.DP != 64) return false;
 #endif
-    return m.DP <= 64 && args.cfg.sampler == 0 && m.has_quad && m.use_bound && !m.use_decay && !m.has_transform &&
-           !m.has_su && !m.has_cubic && !m.has_link && !args.mat &&
+    return m.DP <= 64 && args.cfg.sampler == 0 && bf_model_plain(m) && !args.mat &&
            args.nslot >= (m.DP == 64 ? SplitGeoT<4>::scratch_slots() : (m.DP == 32 ? SplitGeoT<2>::scratch_slots() : SplitGeoT<1>::scratch_slots()));
 }
 
 int bf_launch_split(bfhip_ctx *ctx, const SamplerArgs &args_in) {
+    BfTune &tune = bf_tune();
     SamplerArgs args = args_in;
-    args.gcount = g_gcount_ptr();
-    args.no_bound_proof = bf_no_bound_proof();
-    args.stamps = g_gstamps_ptr();
-    const int groups = (args.n_chain + 15) / 16;
+    args.gcount = tune.group_counters;
+    args.stamps = tune.gstamps;
+    args.no_bound_proof = tune.no_bound_proof;
+    const int W = ctx->model.DP / 16;
+    snprintf(tune.last_kernel, sizeof(tune.last_kernel), "bf_split_kernel<%d>", W);
+    void (*k)(DevModel, SamplerArgs);
+    size_t lds;
+    switch (W) {
 #ifndef BF_ONLY_HEADLINE
-    if (ctx->model.DP == 32) {
-        const size_t lds = SplitGeoT<2>::lds_doubles() * sizeof(double);
-        BF_HIP_CHECK(hipFuncSetAttribute((const void *)bf_split_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(bf_split_kernel<2>, dim3(groups), dim3(256), lds, ctx->stream, ctx->model, args);
-        BF_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    if (ctx->model.DP == 16) {
-        const size_t lds = SplitGeoT<1>::lds_doubles() * sizeof(double);
-        BF_HIP_CHECK(hipFuncSetAttribute((const void *)bf_split_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(bf_split_kernel<1>, dim3(groups), dim3(128), lds, ctx->stream, ctx->model, args);
-        BF_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
+    case 2: k = bf_split_kernel<2>; lds = SplitGeoT<2>::lds_doubles() * sizeof(double); break;
+    case 1: k = bf_split_kernel<1>; lds = SplitGeoT<1>::lds_doubles() * sizeof(double); break;
 #endif
-    const size_t lds = SplitGeoT<4>::lds_doubles() * sizeof(double);
-    BF_HIP_CHECK(hipFuncSetAttribute((const void *)bf_split_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(bf_split_kernel<4>, dim3(groups), dim3(512), lds, ctx->stream, ctx->model, args);
+    default: k = bf_split_kernel<4>; lds = SplitGeoT<4>::lds_doubles() * sizeof(double);
+    }
+    if (int rc = bf_set_lds(k, lds)) return rc;
+    hipLaunchKernelGGL(k, dim3((args.n_chain + 15) / 16), dim3(128 * W), lds, ctx->stream, ctx->model, args);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -118,25 +107,22 @@ static size_t group_pld_lds_bytes(const DevModel &m) {
 bool bf_group_supports(const DevModel &m, const SamplerArgs &args) {
     if (m.pld.on)   // the pipeline density (round 6): NUTS, no decay term, the sixteen-chain LDS layout has to fit beside the tree vectors
         return !m.pld.stream && m.DP <= 64 && args.cfg.sampler == 0 && !m.use_decay && !args.mat && !(bf_tune().no_group_pld != 0) &&
-               group_pld_lds_bytes(m) <= (size_t)160 * 1024;
-    return m.DP <= 64 && m.has_quad && m.use_bound && !m.has_su && !m.has_cubic && !m.has_link && !args.mat;
+               group_pld_lds_bytes(m) <= BF_LDS_MAX;
+    return m.DP <= 64 && bf_common_surrogate(m) && !args.mat;
 }
 
 int bf_group_scratch_slots(int DP) { return 5 * (BFHIP_MAX_TREEDEPTH - 2); }
 
-// tuning hook (not part of include/bfhip.h): cycle stamps of workgroup 0's first trips, see GTRACE in bfhip_group.h
-
-// test hook (not part of include/bfhip.h): 1 = never skip the bound's tiles (the results must not change)
-
-
 int bf_launch_group(bfhip_ctx *ctx, const SamplerArgs &args_in) {
+    BfTune &tune = bf_tune();
     SamplerArgs args = args_in;
-    args.gcount = bf_tune().group_counters;
-    args.stamps = bf_tune().gstamps;
-    args.no_bound_proof = bf_tune().no_bound_proof;
+    args.gcount = tune.group_counters;
+    args.stamps = tune.gstamps;
+    args.no_bound_proof = tune.no_bound_proof;
     const DevModel &m = ctx->model;
     const bool nuts = args.cfg.sampler == 0;
-    const int fs = m.pld.on ? (8 | (m.has_transform ? 4 : 0)) : (1 | (m.use_decay ? 2 : 0) | (m.has_transform ? 4 : 0));
+    const int fs = bf_feature_bits(m);
+    snprintf(tune.last_kernel, sizeof(tune.last_kernel), "bf_group_kernel<%d, %s, %d>", m.DP / 16, nuts ? "true" : "false", fs);
     switch (m.DP / 16) {
 #ifndef BF_ONLY_HEADLINE
     case 1: return launch_w<1>(ctx, args, nuts, fs);

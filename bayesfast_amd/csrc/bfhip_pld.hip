@@ -234,7 +234,7 @@ extern "C" int bfhip_pipeline_upload(bfhip_ctx *ctx, const bfhip_pipeline_desc *
         for (int ks = 1; ks <= PLD_MAX_KS2; ++ks) {
             const int kpj = roundup((NS2 + ks - 1) / ks, 4);
             if (ks > 1 && (ks - 1) * kpj >= NS2) continue;   // an empty part
-            if (base_bytes + pld_lds_doubles(DP, MP, PP, ks, (int)n_ent, xs) * sizeof(double) > (size_t)160 * 1024) continue;
+            if (base_bytes + pld_lds_doubles(DP, MP, PP, ks, (int)n_ent, xs) * sizeof(double) > BF_LDS_MAX) continue;
             const long cost = (long)((NT2 * ks + 15) / 16) * kpj;
             if (!best_ks || cost < best_cost) { best_ks = ks; best_cost = cost; }
         }
@@ -251,7 +251,7 @@ extern "C" int bfhip_pipeline_upload(bfhip_ctx *ctx, const bfhip_pipeline_desc *
                                 "(F row tiles in registers); this one has %d outputs x %d monomials -> %d rows", 128 * PLD_S_TPW, m, nf, m_eff);
         }
         for (int kc = 16; kc <= PP; kc += 16)   // (the largest chunk whose double buffer fits beside the sampler's own regions)
-            if (base_bytes + pld_s_lds_doubles(DP, MP, kc) * sizeof(double) <= (size_t)160 * 1024) KC = kc;
+            if (base_bytes + pld_s_lds_doubles(DP, MP, kc) * sizeof(double) <= BF_LDS_MAX) KC = kc;
         if (!KC) {
             dm.pld.on = 0;
             return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_pipeline_upload: %d outputs x %d monomials need %zu KB of LDS per workgroup even "
@@ -313,13 +313,7 @@ extern "C" int bfhip_pipeline_upload(bfhip_ctx *ctx, const bfhip_pipeline_desc *
         }
     const size_t n_dbl = CF.size() + CTF.size() + 2 * (size_t)MP + prior.size();
     const size_t bytes = n_dbl * 8 + gtab.size() * 8 + mono_tab.size() * 4 + 64;
-    if (ctx->pld_bytes < bytes) {
-        if (ctx->pld_buf) BF_HIP_CHECK(hipFree(ctx->pld_buf));
-        ctx->pld_buf = NULL;
-        ctx->pld_bytes = 0;
-        BF_HIP_CHECK(hipMalloc(&ctx->pld_buf, bytes));
-        ctx->pld_bytes = bytes;
-    }
+    if (int rc = bf_grow(ctx, &ctx->pld_buf, &ctx->pld_bytes, bytes)) return rc;
     std::vector<char> hb(bytes, 0);
     double *hd = (double *)hb.data();
     size_t o = 0;
@@ -522,10 +516,10 @@ int bf_pld_logp_grad(bfhip_ctx *ctx, int n, const double *x, int original_space,
     const DevModel &m = ctx->model;
     if (m.pld.stream) {   // the streamed form: eight points per workgroup
         const size_t lds = (pld_s_lds_doubles(m.DP, m.pld.MP, m.pld.KC) + (size_t)8 * 2 * m.DP) * sizeof(double);
-        if (lds > (size_t)160 * 1024) return bf_set_error(BFHIP_ERR_UNSUPPORTED, "pipeline density: %zu KB of LDS", lds / 1024);
+        if (lds > BF_LDS_MAX) return bf_set_error(BFHIP_ERR_UNSUPPORTED, "pipeline density: %zu KB of LDS", lds / 1024);
         const bool e2 = m.DP > 64;
         void (*k)(DevModel, int, const double *, int, double *, double *) = e2 ? bf_pld_logp_grad_kernel<8, 2, true> : bf_pld_logp_grad_kernel<8, 1, true>;
-        if (lds > 64 * 1024) BF_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (int rc = bf_set_lds(k, lds)) return rc;
         snprintf(bf_tune().last_kernel, sizeof(bf_tune().last_kernel), "bf_pld_logp_grad_kernel<8, %d, true>", e2 ? 2 : 1);
         int grid = (n + 7) / 8;
         if (grid > 4 * ctx->n_cu) grid = 4 * ctx->n_cu;
@@ -535,11 +529,11 @@ int bf_pld_logp_grad(bfhip_ctx *ctx, int n, const double *x, int original_space,
     }
     const int npt = m.pld.only8 ? 8 : 16;
     const size_t lds = (pld_lds_doubles(m.DP, m.pld.MP, m.pld.PP, m.pld.KS2, m.pld.n_ent, npt == 8 ? PLD_XS8 : PLD_XS) + (size_t)npt * 2 * m.DP) * sizeof(double);
-    if (lds > (size_t)160 * 1024) return bf_set_error(BFHIP_ERR_UNSUPPORTED, "pipeline density: %zu KB of LDS", lds / 1024);
+    if (lds > BF_LDS_MAX) return bf_set_error(BFHIP_ERR_UNSUPPORTED, "pipeline density: %zu KB of LDS", lds / 1024);
     const bool e2 = m.DP > 64;   // two dimensions per lane
     void (*k)(DevModel, int, const double *, int, double *, double *) =
         npt == 8 ? (e2 ? bf_pld_logp_grad_kernel<8, 2> : bf_pld_logp_grad_kernel<8, 1>) : (e2 ? bf_pld_logp_grad_kernel<16, 2> : bf_pld_logp_grad_kernel<16, 1>);
-    if (lds > 64 * 1024) BF_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int rc = bf_set_lds(k, lds)) return rc;
     int grid = (n + npt - 1) / npt;
     if (grid > 4 * ctx->n_cu) grid = 4 * ctx->n_cu;
     hipLaunchKernelGGL(k, dim3(grid), dim3(npt * 64), lds, ctx->stream, m, n, x, original_space, logp, grad);

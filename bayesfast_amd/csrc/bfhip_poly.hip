@@ -86,14 +86,7 @@ extern "C" int bfhip_polymodel_upload(bfhip_ctx *ctx, const bfhip_polymodel_desc
     for (int a = 0; a < n3; ++a) { hi[n2 + DP + a] = ds->mask3[a]; if (ds->mask3[a] < 0 || ds->mask3[a] >= d) return bf_set_error(BFHIP_ERR_ARG, "mask3 out of range"); hi[n2 + DP + n3 + ds->mask3[a]] = a; }
     const size_t dbl_bytes = h.size() * sizeof(double);
     const size_t bytes = dbl_bytes + hi.size() * sizeof(int);
-    if (ctx->pm_bytes < bytes) {
-        BF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (ctx->pm_buf) BF_HIP_CHECK(hipFree(ctx->pm_buf));
-        ctx->pm_buf = NULL;
-        ctx->pm_bytes = 0;
-        BF_HIP_CHECK(hipMalloc(&ctx->pm_buf, bytes));
-        ctx->pm_bytes = bytes;
-    }
+    if (int rc = bf_grow(ctx, &ctx->pm_buf, &ctx->pm_bytes, bytes)) return rc;
     BF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     BF_HIP_CHECK(hipMemcpy(ctx->pm_buf, h.data(), dbl_bytes, hipMemcpyHostToDevice));
     BF_HIP_CHECK(hipMemcpy((char *)ctx->pm_buf + dbl_bytes, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -239,7 +232,7 @@ static int launch_polymodel_eval(bfhip_ctx *ctx, int n, const double *x, double 
     auto k = bf_polymodel_eval_kernel<T>;
     const bool cubic = ctx->pm.n2 > 0 || ctx->pm.n3 > 0;
     const size_t lds = ((T <= 4 ? (size_t)256 * T * T : 0) + (cubic ? (size_t)4 * 16 * 16 * T : 0)) * sizeof(double);
-    if (lds > 64 * 1024) BF_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int rc = bf_set_lds(k, lds)) return rc;
     const int grid = (n + 63) / 64;
     int ny = (4 * ctx->n_cu + grid - 1) / grid;  // aim at about four workgroups per CU
     if (ny > ctx->pm.m) ny = ctx->pm.m;
@@ -308,14 +301,7 @@ extern "C" int bfhip_chi2_stage(bfhip_ctx *ctx, int n, int m, int d, const doubl
         return bf_set_error(BFHIP_ERR_ARG, "bfhip_chi2_stage: invalid argument");
     if (n == 0) return 0;
     const size_t need = (size_t)n * m * sizeof(double);
-    if (ctx->scratch_bytes < need) {
-        BF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (ctx->scratch) BF_HIP_CHECK(hipFree(ctx->scratch));
-        ctx->scratch = NULL;
-        ctx->scratch_bytes = 0;
-        BF_HIP_CHECK(hipMalloc(&ctx->scratch, need));
-        ctx->scratch_bytes = need;
-    }
+    if (int rc = bf_grow(ctx, &ctx->scratch, &ctx->scratch_bytes, need)) return rc;
     hipLaunchKernelGGL(bf_chi2_stage_kernel, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, n, m, d, f, jac, y, prec, prec_diag, logp0,
                        logp, grad, (double *)ctx->scratch);
     BF_HIP_CHECK(hipGetLastError());

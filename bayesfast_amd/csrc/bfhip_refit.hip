@@ -23,17 +23,6 @@ __global__ void bf_keys_iota_kernel(long n, const double *__restrict__ a, uint64
     }
 }
 
-static int ensure_scratch(bfhip_ctx *ctx, size_t need) {
-    if (ctx->scratch_bytes >= need) return 0;
-    BF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (ctx->scratch) BF_HIP_CHECK(hipFree(ctx->scratch));
-    ctx->scratch = NULL;
-    ctx->scratch_bytes = 0;
-    BF_HIP_CHECK(hipMalloc(&ctx->scratch, need));
-    ctx->scratch_bytes = need;
-    return 0;
-}
-
 extern "C" int bfhip_sort_keys(bfhip_ctx *ctx, long n, const double *a, uint64_t *keys_sorted, int64_t *order) {
     BfDeviceGuard dev_guard(ctx);
     if (!ctx || n < 0 || (n > 0 && (!a || !keys_sorted || !order)))
@@ -46,7 +35,7 @@ extern "C" int bfhip_sort_keys(bfhip_ctx *ctx, long n, const double *a, uint64_t
     if (e != hipSuccess) return bf_set_error(BFHIP_ERR_HIP, "rocprim::radix_sort_pairs (size query): %s", hipGetErrorString(e));
     // unsorted keys and indices live in the context's workspace, next to rocPRIM's temporary storage
     const size_t kb = ((size_t)n * 8 + 255) / 256 * 256;
-    if (int rc = ensure_scratch(ctx, 2 * kb + tmp)) return rc;
+    if (int rc = bf_grow(ctx, &ctx->scratch, &ctx->scratch_bytes, 2 * kb + tmp)) return rc;
     uint64_t *k0 = (uint64_t *)ctx->scratch;
     int64_t *i0 = (int64_t *)((char *)ctx->scratch + kb);
     void *t = (char *)ctx->scratch + 2 * kb;
@@ -139,7 +128,7 @@ extern "C" int bfhip_importance_weights(bfhip_ctx *ctx, long n, const double *lo
         return bf_set_error(BFHIP_ERR_ARG, "bfhip_importance_weights: invalid argument");
     if (n == 0) return 0;
     const int nb = (int)((n + 255) / 256 < 256 ? (n + 255) / 256 : 256);
-    if (int rc = ensure_scratch(ctx, 256 * sizeof(double))) return rc;
+    if (int rc = bf_grow(ctx, &ctx->scratch, &ctx->scratch_bytes, 256 * sizeof(double))) return rc;
     double *partial = (double *)ctx->scratch;
     hipLaunchKernelGGL(bf_iw_exp_kernel, dim3(nb), dim3(256), 0, ctx->stream, n, logp, logq, w, partial);
     hipLaunchKernelGGL(bf_iw_clip_kernel, dim3(nb), dim3(256), 0, ctx->stream, n, w, partial, nb, k_trunc, w_trunc);

@@ -1819,10 +1819,8 @@ __global__ __launch_bounds__(BF_SAMPLER_WAVES(W, FULLM, FS) * 64) void bf_sample
 #include "bfhip_nuts_pipe.h"
 #include "bfhip_lone.h"
 
-// the common surrogate: linear + quadratic configs with the extrapolation bound and nothing else
-static bool sampler_plain(const DevModel &m) {
-    return m.has_quad && m.use_bound && !m.use_decay && !m.has_transform && !m.has_su && !m.has_cubic && !m.has_link && !(bf_tune().no_plain != 0);
-}
+// bf_model_plain, unless BFHIP_NO_PLAIN asks for the run-time feature set
+static bool sampler_plain(const DevModel &m) { return bf_model_plain(m) && !bf_tune().no_plain; }
 
 // K-split of the matvec jobs: the largest power of two KS <= W with n_mat * W * KS <= 16
 static int sampler_ksplit(const DevModel &m) {
@@ -1853,7 +1851,7 @@ static size_t sampler_cubic_doubles(const DevModel &m) {
 }
 static bool sampler_cubic_lds(const DevModel &m, bool plain) {
     return m.has_cubic && m.n2 <= 64 && m.n3 <= 64 &&
-           (sampler_lds_base(m, plain) + sampler_cubic_doubles(m)) * sizeof(double) <= (size_t)160 * 1024;
+           (sampler_lds_base(m, plain) + sampler_cubic_doubles(m)) * sizeof(double) <= BF_LDS_MAX;
 }
 static size_t sampler_lds_bytes(const DevModel &m, bool plain, int nwv = 16) {
     if (m.pld.on && m.pld.stream)   // (the streamed form's block, at the same place)
@@ -1881,32 +1879,29 @@ static int wave_layout_cpg(const bfhip_ctx *ctx, int n_chain, int nwv) {
 
 template <int W, bool NUTS, bool STAMPS, int FS, int FULLM = 0>
 static int launch_sampler_t(bfhip_ctx *ctx, const SamplerArgs &args_in) {
+    BfTune &tune = bf_tune();
     auto k = bf_sampler_kernel<W, NUTS, STAMPS, FS, FULLM>;
     constexpr int NWV = BF_SAMPLER_WAVES(W, FULLM, FS);
     size_t lds = sampler_lds_bytes(ctx->model, FS == 1, NWV);
     SamplerArgs args = args_in;
     args.pld_cl = 0;
-    if (ctx->model.pld.on && !ctx->model.pld.stream && NWV == 8 && !(bf_tune().pld_no_cl != 0)) {
+    if (ctx->model.pld.on && !ctx->model.pld.stream && NWV == 8 && !tune.pld_no_cl) {
         // the eight-wave forms read the A operands of both contractions from a row-major copy of C' in LDS when it fits behind the
         // rest (the DES shape: 52 KB), instead of streaming 2 x 51 KB of fragments from L2 in every trip -- the same numbers
         const size_t with_cl = lds + pld_cl_doubles(ctx->model.pld.MP, ctx->model.pld.PP) * sizeof(double) + 16;
-        if (with_cl <= (size_t)160 * 1024) { lds = with_cl; args.pld_cl = 1; }
+        if (with_cl <= BF_LDS_MAX) { lds = with_cl; args.pld_cl = 1; }
     }
-    if (lds > 64 * 1024)
-        BF_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int rc = bf_set_lds(k, lds)) return rc;
     args.cpg = wave_layout_cpg(ctx, args.n_chain, NWV);
     args.cub_lds = sampler_cubic_lds(ctx->model, FS == 1) ? 1 : 0;
-    args.cub_loops = bf_tune().cubic_loops;
+    args.cub_loops = tune.cubic_loops;
     const int groups = (args.n_chain + args.cpg - 1) / args.cpg;
-    snprintf(bf_tune().last_kernel, sizeof(bf_tune().last_kernel), "bf_sampler_kernel<%d, %s, %s, %d, %d>", W, NUTS ? "true" : "false",
+    snprintf(tune.last_kernel, sizeof(tune.last_kernel), "bf_sampler_kernel<%d, %s, %s, %d, %d>", W, NUTS ? "true" : "false",
              STAMPS ? "true" : "false", FS, FULLM);
     hipLaunchKernelGGL(k, dim3(groups), dim3(NWV * 64), lds, ctx->stream, ctx->model, args);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }
-
-// test / tuning hook: NUTS on the common surrogate through bf_sampler_kernel instead of the pipelined kernel
-// (also selected by the environment variable BFHIP_NUTS_KERNEL=sliced)
 
 // The tail of a launch.  A launch of the wave-per-chain kernel lasts as long as its busiest chain, and at its end most workgroups
 // hold one or two unfinished chains on 16-column tiles.  Sixteen-chain launches therefore run in two parts: in the first a
@@ -1925,8 +1920,9 @@ extern "C" int bfhip_debug_tail_count(bfhip_ctx *ctx) {
     return n;
 }
 static int tail_stop_now() {
-    const int hi = bf_tune().lone ? 16 : 4;   // (the few-chain instantiation of the second part takes four chains of every first-part workgroup at most)
-    return bf_tune().tail_stop < 1 ? 1 : (bf_tune().tail_stop > hi ? hi : bf_tune().tail_stop);
+    const BfTune &tune = bf_tune();
+    const int hi = tune.lone ? 16 : 4;   // (the few-chain instantiation of the second part takes four chains of every first-part workgroup at most)
+    return tune.tail_stop < 1 ? 1 : (tune.tail_stop > hi ? hi : tune.tail_stop);
 }
 
 __global__ void bf_tail_list_kernel(int n_chain, int iter_end, const double *sc, int *buf) {
@@ -1948,11 +1944,12 @@ template <int W> struct LoneOcc { static constexpr int MINW = W == 1 ? 2 : 3; };
 
 // form 0: the roomy instantiation (W job waves at d > 32); form 1: three job waves (d > 32: two four-wave workgroups a CU at 256
 // registers); form 2: the tight instantiation (168 / 128 registers: the tail's stragglers when they outnumber the CUs' room)
+using SamplerKernel = void (*)(DevModel, SamplerArgs);
 template <int W, bool TR, int DEC, int FORM>
-static const void *lone_kernel_ptr() {
-    if constexpr (FORM == 0) { auto k = bf_lone_kernel<W, TR, DEC, 1, 0>; return (const void *)k; }
-    else if constexpr (FORM == 1) { auto k = bf_lone_kernel<W, TR, DEC, 1, (W == 4 ? 1 : 0)>; return (const void *)k; }
-    else { auto k = bf_lone_kernel<W, TR, DEC, LoneOcc<W>::MINW, 0>; return (const void *)k; }
+static SamplerKernel lone_kernel() {
+    if constexpr (FORM == 0) return bf_lone_kernel<W, TR, DEC, 1, 0>;
+    else if constexpr (FORM == 1) return bf_lone_kernel<W, TR, DEC, 1, (W == 4 ? 1 : 0)>;
+    else return bf_lone_kernel<W, TR, DEC, LoneOcc<W>::MINW, 0>;
 }
 template <int W, int DEC, int FORM> constexpr int lone_threads() { return LoneWaves<W, DEC, (FORM == 1 && W == 4) ? 1 : 0>::NW * 64; }
 
@@ -1964,9 +1961,9 @@ static int lone_blocks_per_cu(bfhip_ctx *ctx) {
     const int dev = (ctx->device >= 0 && ctx->device < 64) ? ctx->device : 0;
     if (have[dev]) return cached[dev];
     const size_t lds = LoneGeo<W, DEC>::n_doubles * sizeof(double);
+    const SamplerKernel k = lone_kernel<W, TR, DEC, FORM>();
     int nb = 0;
-    const void *k = lone_kernel_ptr<W, TR, DEC, FORM>();
-    if (lds > 64 * 1024 && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 0;
+    if (bf_set_lds(k, lds) != 0) return 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, lone_threads<W, DEC, FORM>(), lds) != hipSuccess) return 0;
     cached[dev] = nb;
     have[dev] = true;
@@ -1974,23 +1971,26 @@ static int lone_blocks_per_cu(bfhip_ctx *ctx) {
 }
 
 template <int W, bool TR, int DEC, int FORM>
-static void lone_launch_form(bfhip_ctx *ctx, const SamplerArgs &args, int n_blocks) {
+static int lone_launch_form(bfhip_ctx *ctx, const SamplerArgs &args, int n_blocks) {
     const size_t lds = LoneGeo<W, DEC>::n_doubles * sizeof(double);
-    if constexpr (FORM == 0) hipLaunchKernelGGL((bf_lone_kernel<W, TR, DEC, 1, 0>), dim3(n_blocks), dim3(lone_threads<W, DEC, 0>()), lds, ctx->stream, ctx->model, args);
-    else if constexpr (FORM == 1) hipLaunchKernelGGL((bf_lone_kernel<W, TR, DEC, 1, (W == 4 ? 1 : 0)>), dim3(n_blocks), dim3(lone_threads<W, DEC, 1>()), lds, ctx->stream, ctx->model, args);
-    else hipLaunchKernelGGL((bf_lone_kernel<W, TR, DEC, LoneOcc<W>::MINW, 0>), dim3(n_blocks), dim3(lone_threads<W, DEC, 2>()), lds, ctx->stream, ctx->model, args);
+    const SamplerKernel k = lone_kernel<W, TR, DEC, FORM>();
+    if (int rc = bf_set_lds(k, lds)) return rc;
+    hipLaunchKernelGGL(k, dim3(n_blocks), dim3(lone_threads<W, DEC, FORM>()), lds, ctx->stream, ctx->model, args);
+    BF_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 // returns 1 when the launch was taken, 0 when the caller should use the pipelined kernel, < 0 on error
 template <int W, bool TR, int DEC>
 static int launch_lone(bfhip_ctx *ctx, const SamplerArgs &args_in, int n_blocks, bool tail) {
-    if (!bf_tune().lone || args_in.stamps) return 0;
+    BfTune &tune = bf_tune();
+    if (!tune.lone || args_in.stamps) return 0;
     SamplerArgs args = args_in;
     args.n_cu = ctx->n_cu;
     args.tail_stop = 0;
     args.tail_done = NULL;
     if (!tail) { args.tail_list = NULL; args.tail_count = NULL; }
-    args.stamps = bf_tune().stamps_lone;
+    args.stamps = tune.stamps_lone;
     // every workgroup must be resident (a chain that waited for a slot would double the launch): the roomiest form that holds them
     const int need = (n_blocks + ctx->n_cu - 1) / ctx->n_cu;
     int form = 0;
@@ -2000,20 +2000,20 @@ static int launch_lone(bfhip_ctx *ctx, const SamplerArgs &args_in, int n_blocks,
             form = 2;
             // (a whole launch takes the kernel only in a roomy form: two workgroups per CU at 168 registers ran a 64-d chain at half
             // the speed of one; the tight form is for the tail, whose chains are there anyway, and for tests)
-            if (bf_tune().lone != 2 && !tail) return 0;
+            if (tune.lone != 2 && !tail) return 0;
         }
     }
-    if (bf_tune().lone_form >= 0 && bf_tune().lone_form <= 2) form = bf_tune().lone_form;   // (tests: the forms give the same numbers)
-    if (form == 0) lone_launch_form<W, TR, DEC, 0>(ctx, args, n_blocks);
-    else if (form == 1) lone_launch_form<W, TR, DEC, 1>(ctx, args, n_blocks);
-    else lone_launch_form<W, TR, DEC, 2>(ctx, args, n_blocks);
-    BF_HIP_CHECK(hipGetLastError());
-    if (!tail) snprintf(bf_tune().last_kernel, sizeof(bf_tune().last_kernel), "bf_lone_kernel<%d, %s, %d, %d>", W, TR ? "true" : "false", DEC, form);
+    if (tune.lone_form >= 0 && tune.lone_form <= 2) form = tune.lone_form;   // (tests: the forms give the same numbers)
+    const int rc = form == 0 ? lone_launch_form<W, TR, DEC, 0>(ctx, args, n_blocks)
+                 : form == 1 ? lone_launch_form<W, TR, DEC, 1>(ctx, args, n_blocks) : lone_launch_form<W, TR, DEC, 2>(ctx, args, n_blocks);
+    if (rc) return rc;
+    if (!tail) snprintf(tune.last_kernel, sizeof(tune.last_kernel), "bf_lone_kernel<%d, %s, %d, %d>", W, TR ? "true" : "false", DEC, form);
     return 1;
 }
 
 template <int W, bool TR = false, int DEC = 0>
 static int launch_nuts_pipe(bfhip_ctx *ctx, const SamplerArgs &args_in) {
+    BfTune &tune = bf_tune();
     SamplerArgs args = args_in;
     args.cpg = wave_layout_cpg(ctx, args.n_chain, 16);
     args.tail_stop = 0;
@@ -2022,43 +2022,32 @@ static int launch_nuts_pipe(bfhip_ctx *ctx, const SamplerArgs &args_in) {
     args.tail_done = NULL;
     args.n_cu = ctx->n_cu;
     // (at most four / eight chains in a workgroup: 4 x 4 x 4 MFMA tiles)
-    constexpr bool CANQ = true;
-    auto k = (CANQ && args.cpg <= 4 && !bf_tune().no_quad) ? bf_nuts_pipe_kernel<W, TR, DEC, CANQ ? 1 : 0>
-             : ((CANQ && args.cpg <= 8 && !bf_tune().no_quad) ? bf_nuts_pipe_kernel<W, TR, DEC, CANQ ? 2 : 0> : bf_nuts_pipe_kernel<W, TR, DEC>);
-    if ((args.cpg <= 4 && !bf_tune().no_quad && bf_tune().wave_cpg == 0) || bf_tune().lone == 2) {
+    const int quad = tune.no_quad ? 0 : (args.cpg <= 4 ? 1 : (args.cpg <= 8 ? 2 : 0));
+    auto k = quad == 1 ? bf_nuts_pipe_kernel<W, TR, DEC, 1> : (quad == 2 ? bf_nuts_pipe_kernel<W, TR, DEC, 2> : bf_nuts_pipe_kernel<W, TR, DEC, 0>);
+    if ((quad == 1 && tune.wave_cpg == 0) || tune.lone == 2) {
         const int r = launch_lone<W, TR, DEC>(ctx, args, args.n_chain, false);
         if (r != 0) return r < 0 ? r : 0;
     }
     const size_t lds = PipeGeo<W, DEC>::lds_doubles() * sizeof(double);
-    if (lds > 64 * 1024)
-        BF_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int rc = bf_set_lds(k, lds)) return rc;
     const int groups = (args.n_chain + args.cpg - 1) / args.cpg;
-    const bool two_parts = bf_tune().tail_relaunch && args.cpg == 16 && !bf_tune().no_quad && !args.stamps;
+    const bool two_parts = tune.tail_relaunch && args.cpg == 16 && !tune.no_quad && !args.stamps;
     if (two_parts) {
-        if (ctx->tail_cap < args.n_chain + 2) {
-            BF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            if (ctx->tail_buf) BF_HIP_CHECK(hipFree(ctx->tail_buf));
-            ctx->tail_buf = NULL;
-            ctx->tail_cap = 0;
-            BF_HIP_CHECK(hipMalloc((void **)&ctx->tail_buf, (size_t)(args.n_chain + 2) * sizeof(int)));
-            ctx->tail_cap = args.n_chain + 2;
-        }
+        if (int rc = bf_grow(ctx, (void **)&ctx->tail_buf, &ctx->tail_bytes, (size_t)(args.n_chain + 2) * sizeof(int))) return rc;
         args.tail_stop = tail_stop_now();
-        args.tail_q = bf_tune().tail_q < 1 ? 1 : (bf_tune().tail_q > 4 ? 4 : bf_tune().tail_q);
+        args.tail_q = tune.tail_q < 1 ? 1 : (tune.tail_q > 4 ? 4 : tune.tail_q);
         args.tail_done = ctx->tail_buf + 1;
         BF_HIP_CHECK(hipMemsetAsync(ctx->tail_buf, 0, 2 * sizeof(int), ctx->stream));
     }
     hipLaunchKernelGGL(k, dim3(groups), dim3(1024), lds, ctx->stream, ctx->model, args);
     BF_HIP_CHECK(hipGetLastError());
-    snprintf(bf_tune().last_kernel, sizeof(bf_tune().last_kernel), "bf_nuts_pipe_kernel<%d, %s, %d, %d>", W, TR ? "true" : "false", DEC,
-             (args.cpg <= 4 && !bf_tune().no_quad) ? 1 : ((args.cpg <= 8 && !bf_tune().no_quad) ? 2 : 0));
+    snprintf(tune.last_kernel, sizeof(tune.last_kernel), "bf_nuts_pipe_kernel<%d, %s, %d, %d>", W, TR ? "true" : "false", DEC, quad);
     if (two_parts) {
         hipLaunchKernelGGL(bf_tail_list_kernel, dim3((args.n_chain + 255) / 256), dim3(256), 0, ctx->stream, args.n_chain, args.iter_end, args.sc,
                            ctx->tail_buf);
         BF_HIP_CHECK(hipGetLastError());
         auto k2 = bf_nuts_pipe_kernel<W, TR, DEC, 1>;
-        if (lds > 64 * 1024)
-            BF_HIP_CHECK(hipFuncSetAttribute((const void *)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (int rc = bf_set_lds(k2, lds)) return rc;
         SamplerArgs a2 = args;
         a2.tail_stop = 0;
         a2.tail_count = ctx->tail_buf;
@@ -2078,21 +2067,13 @@ static int launch_nuts_pipe(bfhip_ctx *ctx, const SamplerArgs &args_in) {
     return 0;
 }
 
-// test / tuning hook: keep NUTS / HMC on the common surrogate off the group kernel (bfhip_group.hip), i.e. on the
-// kernels of this file (also selected by BFHIP_NUTS_KERNEL=sliced or =pipe)
-
-
-// diagnostics hook (not part of include/bfhip.h): per-wave cycle counters of the sampler kernel's phases
-
-// test / tuning hook (not part of include/bfhip.h; also BFHIP_PLD_WAVES): 8 or 16 waves per workgroup for the pipeline density, 0 = by chain count
-
-
 template <int W, bool NUTS>
 static int launch_sampler(bfhip_ctx *ctx, const SamplerArgs &args) {
+    const BfTune &tune = bf_tune();
     const DevModel &m = ctx->model;
     const bool plain = sampler_plain(m) && !args.mat;
     if (m.pld.on && m.pld.stream) {   // the streamed pipeline density: FS = 11, eight waves, either metric
-        if (sampler_lds_bytes(m, false, 8) > (size_t)160 * 1024)
+        if (sampler_lds_bytes(m, false, 8) > BF_LDS_MAX)
             return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_sampler_run: this streamed pipeline density needs %zu KB of LDS at d = %d (160 KB)",
                                 sampler_lds_bytes(m, false, 8) / 1024, m.d);
         return args.mat ? launch_sampler_t<W, NUTS, false, 11, 1>(ctx, args) : launch_sampler_t<W, NUTS, false, 11>(ctx, args);
@@ -2100,73 +2081,80 @@ static int launch_sampler(bfhip_ctx *ctx, const SamplerArgs &args) {
     if (m.pld.on) {   // pipeline density: the FS = 8 / 9 / 10 instantiations
         if constexpr (W == 8) {
             // d = 128 (round 6): the eight-wave form with the run-time feature set, two dimensions per lane in phase P
-            if (sampler_lds_bytes(m, false, 8) > (size_t)160 * 1024)
+            if (sampler_lds_bytes(m, false, 8) > BF_LDS_MAX)
                 return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_sampler_run: this pipeline density needs %zu KB of LDS at d = %d (160 KB)",
                                     sampler_lds_bytes(m, false, 8) / 1024, m.d);
             return args.mat ? launch_sampler_t<8, NUTS, false, 9, 1>(ctx, args) : launch_sampler_t<8, NUTS, false, 9>(ctx, args);
+        } else {
+            if (args.mat) {   // full-rank metric: the eight-wave form with the run-time feature set (bfhip_metric.h streams the chain's own matrices)
+                return launch_sampler_t<W, NUTS, false, 9, 1>(ctx, args);
+            }
+            // eight chains per workgroup (and 256 registers a wave) while that fills the chip, sixteen beyond
+            // (measured, tools/pld_rate.py: with the outputs compressed to the monomial count the DES shape's contractions are 200
+            // tile k-steps and the eight-wave form wins at every chain count -- 1.41 against 1.30 x 10^8 at 4096 chains; at 1800 tile
+            // k-steps, a quadratic config on 20 inputs, the sixteen-wave form's full tiles win, 8.2 against 7.3 x 10^7)
+            const long gemm_steps = (long)m.pld.NT1 * m.pld.NS1 + (long)m.pld.NT2 * m.pld.NS2;
+            const bool w8 = m.pld.only8 || (tune.pld_waves ? tune.pld_waves == 8 : (args.n_chain <= 8 * ctx->n_cu || gemm_steps <= 800));
+            if (w8 && m.has_transform && m.has_su && m.use_bound && !m.use_decay && !tune.no_plain) return launch_sampler_t<W, NUTS, false, 10>(ctx, args);
+            return w8 ? launch_sampler_t<W, NUTS, false, 9>(ctx, args) : launch_sampler_t<W, NUTS, false, 8>(ctx, args);
         }
-        constexpr int WP = W <= 4 ? W : 1;   // (keeps W = 8 from instantiating the other forms)
-        if (args.mat) {   // full-rank metric: the eight-wave form with the run-time feature set (bfhip_metric.h streams the chain's own matrices)
-            return launch_sampler_t<WP, NUTS, false, 9, 1>(ctx, args);
-        }
-        // eight chains per workgroup (and 256 registers a wave) while that fills the chip, sixteen beyond
-        // (measured, tools/pld_rate.py: with the outputs compressed to the monomial count the DES shape's contractions are 200
-        // tile k-steps and the eight-wave form wins at every chain count -- 1.41 against 1.30 x 10^8 at 4096 chains; at 1800 tile
-        // k-steps, a quadratic config on 20 inputs, the sixteen-wave form's full tiles win, 8.2 against 7.3 x 10^7)
-        const long gemm_steps = (long)m.pld.NT1 * m.pld.NS1 + (long)m.pld.NT2 * m.pld.NS2;
-        const bool w8 = m.pld.only8 || (bf_tune().pld_waves ? bf_tune().pld_waves == 8 : (args.n_chain <= 8 * ctx->n_cu || gemm_steps <= 800));
-        if (w8 && m.has_transform && m.has_su && m.use_bound && !m.use_decay && !(bf_tune().no_plain != 0)) return launch_sampler_t<WP, NUTS, false, 10>(ctx, args);
-        return w8 ? launch_sampler_t<WP, NUTS, false, 9>(ctx, args) : launch_sampler_t<WP, NUTS, false, 8>(ctx, args);
     }
     if (args.mat) {   // (a compile-time feature set changes nothing here: 7.4 x 10^7 either way)
         // While the metric adapts an iteration ends with passes over three more matrices, and the second column of the
         // velocity-ahead pass costs more than the pass it saves (3.0 against 3.3 x 10^7, tools/full_metric_rate.py); afterwards it
         // is worth a fifth (7.4 -> 8.9 x 10^7).  Both forms in one kernel were slower than either.  The same numbers from both.
         const bool adapting = args.cfg.adapt_metric && args.iter_out0 < args.cfg.n_warmup;
-        return (adapting || (bf_tune().no_vel_ahead != 0)) ? launch_sampler_t<W, NUTS, false, 0, 1>(ctx, args) : launch_sampler_t<W, NUTS, false, 0, 2>(ctx, args);
+        return (adapting || tune.no_vel_ahead) ? launch_sampler_t<W, NUTS, false, 0, 1>(ctx, args) : launch_sampler_t<W, NUTS, false, 0, 2>(ctx, args);
     }
 #ifndef BF_TRACE
-    if (W == 4 && NUTS && args.stamps)  // diagnostic build, d <= 64 NUTS only
+    // diagnostic build, d <= 64 NUTS only.  (A guard rather than if constexpr: for the other W and HMC these name the run-time kernel,
+    // and naming it here, first, fixes where it sits among the kernels of the code object)
+    if (W == 4 && NUTS && args.stamps)
         return plain ? launch_sampler_t<W, NUTS, (W == 4 && NUTS), (W == 4 && NUTS) ? 1 : 0>(ctx, args)
                      : launch_sampler_t<W, NUTS, (W == 4 && NUTS), 0>(ctx, args);
-#endif
-#ifdef BF_TRACE   // (tuning builds: the pipelined kernel writes its own stamps)
-    const bool stamped = false;
-#else
     const bool stamped = args.stamps != NULL;
+#else   // (tuning builds: the pipelined kernel writes its own stamps)
+    const bool stamped = false;
 #endif
-    if (plain && NUTS && W <= 4 && !(bf_tune().no_pipe != 0) && !stamped)
-        return launch_nuts_pipe<(W <= 4 ? W : 1)>(ctx, args);
+    // the pipelined kernel: NUTS on the common surrogate at d <= 64 -- plain, behind the constraint transform, or with the decay penalty
+    const bool common = bf_common_surrogate(m) && !tune.no_plain;
+    const bool pipe = NUTS && !tune.no_pipe && !stamped;
+    if constexpr (W <= 4) {
+        if (plain && pipe) return launch_nuts_pipe<W>(ctx, args);
+    }
     if (plain) return launch_sampler_t<W, NUTS, false, 1>(ctx, args);
-    // ... and the same surrogate behind the constraint transform (bounded parameters)
-    if (W <= 4 && NUTS && !(bf_tune().no_pipe != 0) && !(bf_tune().no_plain != 0) && !stamped && m.has_quad && m.use_bound && m.has_transform && !m.use_decay &&
-        !m.has_su && !m.has_cubic && !m.has_link)
-        return launch_nuts_pipe<(W <= 4 ? W : 1), (W <= 4)>(ctx, args);
-    // ... and with the decay penalty (the GBS recipes' densities: configs 3 and 4)
-    if (W <= 4 && NUTS && !(bf_tune().no_pipe != 0) && !(bf_tune().no_plain != 0) && !stamped && m.has_quad && m.use_bound && m.use_decay &&
-        !m.has_transform && !m.has_su && !m.has_cubic && !m.has_link) {
-        // (the decay term's matrix and centre are the bound's, bit for bit: two matrices do, bfhip_nuts_pipe.h)
-        if (m.decay_shared && !bf_tune().no_decay_shared) return launch_nuts_pipe<(W <= 4 ? W : 1), false, (W <= 4 ? 2 : 0)>(ctx, args);
-        return launch_nuts_pipe<(W <= 4 ? W : 1), false, (W <= 4 ? 1 : 0)>(ctx, args);
+    if constexpr (W <= 4) {
+        // ... and the same surrogate behind the constraint transform (bounded parameters)
+        if (pipe && common && m.has_transform && !m.use_decay) return launch_nuts_pipe<W, true>(ctx, args);
+        // ... and with the decay penalty (the GBS recipes' densities: configs 3 and 4)
+        if (pipe && common && m.use_decay && !m.has_transform) {
+            // (the decay term's matrix and centre are the bound's, bit for bit: two matrices do, bfhip_nuts_pipe.h)
+            if (m.decay_shared && !tune.no_decay_shared) return launch_nuts_pipe<W, false, 2>(ctx, args);
+            return launch_nuts_pipe<W, false, 1>(ctx, args);
+        }
     }
 #ifndef BF_ONLY_HEADLINE
     // the common surrogate with the decay penalty and / or the constraint transform: compile-time feature sets at
     // 33 <= d <= 64 (the optional features' branches and register arrays of the run-time kernel disappear)
-    if (W == 4 && !(bf_tune().no_plain != 0) && m.has_quad && m.use_bound && !m.has_su && !m.has_cubic && !m.has_link) {
-        constexpr int W4 = W == 4 ? 4 : W;  // (keeps the other W from instantiating these)
-        if (m.use_decay && m.has_transform) return launch_sampler_t<W4, NUTS, false, (W == 4 ? 7 : 0)>(ctx, args);
-        if (m.use_decay) return launch_sampler_t<W4, NUTS, false, (W == 4 ? 3 : 0)>(ctx, args);
-        if (m.has_transform) return launch_sampler_t<W4, NUTS, false, (W == 4 ? 5 : 0)>(ctx, args);
+    if constexpr (W == 4) {
+        if (common) {
+            switch (bf_feature_bits(m)) {
+            case 7: return launch_sampler_t<4, NUTS, false, 7>(ctx, args);
+            case 3: return launch_sampler_t<4, NUTS, false, 3>(ctx, args);
+            case 5: return launch_sampler_t<4, NUTS, false, 5>(ctx, args);
+            }
+        }
     }
     // d = 128 with cubic configs and nothing else (config 5): the feature set fixed at compile time too
-    if (W == 8 && NUTS && !(bf_tune().no_plain != 0) && m.has_quad && m.use_bound && m.has_cubic && !m.use_decay && !m.has_transform && !m.has_su &&
-        !m.has_link) {
-        // at most four chains per CU (config 5's shard): four waves, each with a chain and two row tiles of S in registers
-        const int form = bf_tune().cubic_form;
-        if (form != 8 && bf_tune().wave_cpg == 0 && sampler_ksplit(m) == 1 && sampler_cubic_lds(m, false) &&
-            (form == 4 || args.n_chain <= 4 * ctx->n_cu))
-            return launch_sampler_t<(W == 8 ? 8 : W), NUTS, false, (W == 8 && NUTS ? 17 : 0)>(ctx, args);
-        return launch_sampler_t<(W == 8 ? 8 : W), NUTS, false, (W == 8 && NUTS ? 16 : 0)>(ctx, args);
+    if constexpr (W == 8 && NUTS) {
+        if (!tune.no_plain && m.has_quad && m.use_bound && m.has_cubic && !m.use_decay && !m.has_transform && !m.has_su && !m.has_link) {
+            // at most four chains per CU (config 5's shard): four waves, each with a chain and two row tiles of S in registers
+            const int form = tune.cubic_form;
+            if (form != 8 && tune.wave_cpg == 0 && sampler_ksplit(m) == 1 && sampler_cubic_lds(m, false) &&
+                (form == 4 || args.n_chain <= 4 * ctx->n_cu))
+                return launch_sampler_t<8, true, false, 17>(ctx, args);
+            return launch_sampler_t<8, true, false, 16>(ctx, args);
+        }
     }
 #endif
     return launch_sampler_t<W, NUTS, false, 0>(ctx, args);
@@ -2176,6 +2164,8 @@ extern "C" int bfhip_sampler_run(bfhip_ctx *ctx, const bfhip_sampler_config *cfg
                                  uint64_t *rng, double *sc, double *vec, int iter_out0, int n_out, double *samples,
                                  double *stats, unsigned long long *n_leapfrog) {
     BfDeviceGuard dev_guard(ctx);
+    BfTune &tune = bf_tune();
+    tune.last_kernel[0] = '\0';   // (the launchers name the instantiation they launch)
     if (!ctx || !cfg || n_chain < 0) return bf_set_error(BFHIP_ERR_ARG, "bfhip_sampler_run: invalid argument");
     if (!ctx->has_model) return bf_set_error(BFHIP_ERR_STATE, "bfhip_sampler_run: no density uploaded");
     if (n_chain == 0) return 0;
@@ -2192,14 +2182,14 @@ extern "C" int bfhip_sampler_run(bfhip_ctx *ctx, const bfhip_sampler_config *cfg
     SamplerArgs args;
     args.cpg = 0;
     args.cub_lds = 0;
-    args.no_quad = bf_tune().no_quad;
+    args.no_quad = tune.no_quad;
     args.cfg = *cfg;
     args.n_chain = n_chain;
     args.iter_end = iter_end;
     args.iter_out0 = iter_out0;
     args.n_out = n_out;
     args.nslot = SL_PIPE_N;  // both ends, proposal, p_sum, 4 vectors per stack level (+ the proposals' gradients: pipelined kernel)
-    args.tail_max = bf_tune().tail_max;
+    args.tail_max = tune.tail_max;
     args.ks = sampler_ksplit(m);
     args.gbn = sampler_gb_slots(m);
     args.rng = rng;
@@ -2208,43 +2198,22 @@ extern "C" int bfhip_sampler_run(bfhip_ctx *ctx, const bfhip_sampler_config *cfg
     args.samples = samples;
     args.stats = stats;
     args.n_leapfrog = n_leapfrog;
-    args.stamps = bf_tune().stamps;
+    args.stamps = tune.stamps;
     args.no_bound_proof = bf_no_bound_proof();
     args.gcount = NULL;
     args.mat = (cfg->full_metric && cfg->metric_mat) ? cfg->metric_mat : NULL;
     if (cfg->full_metric && !cfg->metric_mat) return bf_set_error(BFHIP_ERR_ARG, "bfhip_sampler_run: full_metric without metric_mat");
     const size_t need = (size_t)((n_chain + 15) / 16 * 16) * args.nslot * m.DP * sizeof(double);
-    if (ctx->scratch_bytes < need) {  // grow-only workspace; allocation is outside any timed region after the first call
-        BF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (ctx->scratch) BF_HIP_CHECK(hipFree(ctx->scratch));
-        ctx->scratch = NULL;
-        ctx->scratch_bytes = 0;
-        BF_HIP_CHECK(hipMalloc(&ctx->scratch, need));
-        ctx->scratch_bytes = need;
-    }
+    if (int rc = bf_grow(ctx, &ctx->scratch, &ctx->scratch_bytes, need)) return rc;
     args.scratch = (double *)ctx->scratch;
     const bool nuts = cfg->sampler == 0;
     // the common surrogate (linear + quadratic configs with the bound; decay and constraint transform optional) at
-    // d <= 64 with the diagonal metric: the group kernel
+    // d <= 64 with the diagonal metric: the lane-per-chain kernels of bfhip_group.hip
     if (cfg->chain_layout < 0 || cfg->chain_layout > 3) return bf_set_error(BFHIP_ERR_ARG, "chain_layout should be 0, 1, 2 or 3");
-    if (cfg->chain_layout == 3 && !(bf_tune().no_group != 0) && !(bf_tune().no_pipe != 0) && !(bf_tune().no_plain != 0) && !args.stamps && bf_split_supports(m, args)) {
-        snprintf(bf_tune().last_kernel, sizeof(bf_tune().last_kernel), "bf_split_kernel<%d>", W);
-        return bf_launch_split(ctx, args);
-    }
+    const bool lanes = !tune.no_group && !tune.no_pipe && !tune.no_plain && !args.stamps;
+    if (cfg->chain_layout == 3 && lanes && bf_split_supports(m, args)) return bf_launch_split(ctx, args);
     const bool want_group = cfg->chain_layout == 1 || cfg->chain_layout == 3 || (cfg->chain_layout == 0 && !nuts);
-    if (want_group && !(bf_tune().no_group != 0) && !(bf_tune().no_pipe != 0) && !(bf_tune().no_plain != 0) && !args.stamps && bf_group_supports(m, args)) {
-        snprintf(bf_tune().last_kernel, sizeof(bf_tune().last_kernel), "bf_group_kernel<%d, %s, %d>", W, nuts ? "true" : "false",
-                 m.pld.on ? (8 | (m.has_transform ? 4 : 0)) : (1 | (m.use_decay ? 2 : 0) | (m.has_transform ? 4 : 0)));
-        return bf_launch_group(ctx, args);
-    }
-    {
-        // (the conditions of launch_sampler: the common surrogate, plain or behind the constraint transform)
-        const bool common = m.has_quad && m.use_bound && !m.has_su && !m.has_cubic && !m.has_link && !(bf_tune().no_plain != 0);
-        const bool tr_only = common && m.has_transform && !m.use_decay, dec_only = common && m.use_decay && !m.has_transform;
-        const bool pipe = nuts && W <= 4 && !(bf_tune().no_pipe != 0) && !args.mat && !args.stamps && (sampler_plain(m) || tr_only || dec_only);
-        if (m.pld.on) snprintf(bf_tune().last_kernel, sizeof(bf_tune().last_kernel), "bf_sampler_kernel<%d, %s, false, 8 | 9>", W, nuts ? "true" : "false");
-        else snprintf(bf_tune().last_kernel, sizeof(bf_tune().last_kernel), "%s<%d, ...>", pipe ? "bf_nuts_pipe_kernel" : "bf_sampler_kernel", W);
-    }
+    if (want_group && lanes && bf_group_supports(m, args)) return bf_launch_group(ctx, args);
     switch (W) {
 #ifndef BF_ONLY_HEADLINE  // tuning builds (-DBF_ONLY_HEADLINE) compile the 64-d instantiations only
     case 1: return nuts ? launch_sampler<1, true>(ctx, args) : launch_sampler<1, false>(ctx, args);

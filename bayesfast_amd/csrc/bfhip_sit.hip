@@ -18,17 +18,6 @@
 #include "bfhip_common.h"
 #include "bfhip_ndtri.h"
 
-static int ensure_ws(bfhip_ctx *ctx, size_t need) {
-    if (ctx->scratch_bytes >= need) return 0;
-    BF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (ctx->scratch) BF_HIP_CHECK(hipFree(ctx->scratch));
-    ctx->scratch = NULL;
-    ctx->scratch_bytes = 0;
-    BF_HIP_CHECK(hipMalloc(&ctx->scratch, need));
-    ctx->scratch_bytes = need;
-    return 0;
-}
-
 // ---- KDE cdf -----------------------------------------------------------------------------------------------------
 // out[j][i] = sum_k w[k] ndtr((pts[j][i] - data[j][k]) / h[j]);  data (d, n), pts (d, m): one row per dimension.
 // grid (point tiles, data splits, d); a thread keeps KP points in registers and strides over its split of the data.
@@ -86,7 +75,7 @@ extern "C" int bfhip_kde_cdf(bfhip_ctx *ctx, int d, long n, const double *data, 
     const int want = (4 * ctx->n_cu + tiles * d - 1) / (tiles * d);  // enough workgroups to fill the chip
     if (n_split > want) n_split = want;
     if (n_split < 1) n_split = 1;
-    if (int rc = ensure_ws(ctx, (size_t)d * n_split * m * sizeof(double))) return rc;
+    if (int rc = bf_grow(ctx, &ctx->scratch, &ctx->scratch_bytes, (size_t)d * n_split * m * sizeof(double))) return rc;
     double *partial = (double *)ctx->scratch;
     hipLaunchKernelGGL(bf_kde_cdf_kernel, dim3(tiles, n_split, d), dim3(KDE_TH), 0, ctx->stream, (int)n, m, data, w, h, pts, n_split,
                        partial);
@@ -234,7 +223,7 @@ extern "C" int bfhip_bridge_sums(bfhip_ctx *ctx, long n_a, const double *a, long
     BfDeviceGuard dev_guard(ctx);
     if (!ctx || n_a < 1 || n_b < 1 || !a || !b || !out2) return bf_set_error(BFHIP_ERR_ARG, "bfhip_bridge_sums: invalid argument");
     const int nb_a = (int)((n_a + 255) / 256 < 512 ? (n_a + 255) / 256 : 512), nb_b = (int)((n_b + 255) / 256 < 512 ? (n_b + 255) / 256 : 512);
-    if (int rc = ensure_ws(ctx, (size_t)2 * (nb_a + nb_b) * sizeof(double))) return rc;
+    if (int rc = bf_grow(ctx, &ctx->scratch, &ctx->scratch_bytes, (size_t)2 * (nb_a + nb_b) * sizeof(double))) return rc;
     double *part = (double *)ctx->scratch;
     hipLaunchKernelGGL(bf_lse_sig_kernel, dim3(nb_a), dim3(256), 0, ctx->stream, n_a, a, logr, part);
     hipLaunchKernelGGL(bf_lse_sig_kernel, dim3(nb_b), dim3(256), 0, ctx->stream, n_b, b, -logr, part + 2 * nb_a);
@@ -376,7 +365,7 @@ extern "C" int bfhip_logmeanexp_stats(bfhip_ctx *ctx, long n, const double *x, c
     BfDeviceGuard dev_guard(ctx);
     if (!ctx || n < 1 || !x || !y || !out3) return bf_set_error(BFHIP_ERR_ARG, "bfhip_logmeanexp_stats: invalid argument");
     const int nb = (int)((n + LME_TH - 1) / LME_TH < LME_MAXB ? (n + LME_TH - 1) / LME_TH : LME_MAXB);
-    if (int rc = ensure_ws(ctx, (size_t)5 * nb * sizeof(double))) return rc;
+    if (int rc = bf_grow(ctx, &ctx->scratch, &ctx->scratch_bytes, (size_t)5 * nb * sizeof(double))) return rc;
     double *part = (double *)ctx->scratch, *part2 = part + 2 * nb;
     hipLaunchKernelGGL(bf_lme_part_kernel, dim3(nb), dim3(LME_TH), 0, ctx->stream, n, x, y, part);
     hipLaunchKernelGGL(bf_lme_combine_kernel, dim3(1), dim3(LME_TH), 0, ctx->stream, nb, n, part, out3);
@@ -1037,14 +1026,7 @@ extern "C" int bfhip_polar_ns(bfhip_ctx *ctx, int d, const double *a, double *x,
         unsigned long long *slots = (unsigned long long *)((char *)counter + 64);
         if (nt <= BF_POLAR_LDS_MAXT && bf_tune().polar_tiles != 2) {
             const size_t lds_x = ((size_t)(16 * nt + 16) * (16 * nt + 4) + 2 * BF_POLAR_LDS_MAXT) * sizeof(double);   // 152 KB at d = 128
-            // (the attribute belongs to the kernel on ONE device: raised once per device, as bfhip_sampler.hip does it; devices past the
-            // table set it at every call)
-            static size_t lds_set[64];
-            const bool slot = ctx->device >= 0 && ctx->device < 64;
-            if (!slot || lds_x > lds_set[ctx->device]) {
-                BF_HIP_CHECK(hipFuncSetAttribute((const void *)bf_polar_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x));
-                if (slot) lds_set[ctx->device] = lds_x;
-            }
+            if (int rc = bf_set_lds(bf_polar_lds_kernel, lds_x)) return rc;
             hipLaunchKernelGGL(bf_polar_lds_kernel, dim3(nt), dim3(64 * nt), lds_x, ctx->stream, d, a, x, n_iter, work, resid, counter, slots,
                                bf_tune().gstamps);
         }

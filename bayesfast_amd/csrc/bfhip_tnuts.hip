@@ -505,21 +505,14 @@ extern "C" int bfhip_tnuts_run(bfhip_ctx *ctx, const bfhip_sampler_config *cfg, 
     // the tuned instantiations: the common surrogate (linear + quadratic configs with the bound; constraint transform and decay
     // optional) at d <= 64 with the diagonal metric.  Everything else -- cubic configs, d = 128, device-side input scaling, the
     // Gaussian link, the pipeline density, the full-rank metric -- runs on the generic kernel (bfhip_tnuts_gen.hip)
-    const bool common = m.has_quad && m.use_bound && !m.has_su && !m.has_cubic && !m.has_link && !m.pld.on;
+    const bool common = bf_common_surrogate(m) && !m.pld.on;
     const bool generic = !common || m.DP > 64 || cfg->full_metric || bf_tune().tnuts_generic;
     // Chains per workgroup (a workgroup is always eight waves, two workgroups per CU: the waves without a chain run matvec jobs
     // only): eight, or four when that spreads few chains over more CUs.  BFHIP_TNUTS_WPB / bfhip_debug_set("tnuts_wpb") override.
     const int forced = bf_tune().tnuts_wpb;
     const int cpg = (forced == 4 || forced == 8) ? forced : (n_chain > 8 * ctx->n_cu ? 8 : 4);
     const size_t need = (size_t)((n_chain + 15) / 16 * 16) * (4 * TN_MAXL) * 64 * sizeof(double);
-    if (ctx->scratch_bytes < need) {
-        BF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (ctx->scratch) BF_HIP_CHECK(hipFree(ctx->scratch));
-        ctx->scratch = NULL;
-        ctx->scratch_bytes = 0;
-        BF_HIP_CHECK(hipMalloc(&ctx->scratch, need));
-        ctx->scratch_bytes = need;
-    }
+    if (int rc = bf_grow(ctx, &ctx->scratch, &ctx->scratch_bytes, need)) return rc;
     if (generic) {
         TnutsArgs g;
         g.cfg = *cfg;
@@ -545,7 +538,7 @@ extern "C" int bfhip_tnuts_run(bfhip_ctx *ctx, const bfhip_sampler_config *cfg, 
 #define TN_PICK(Wv) (tr ? (dec ? bf_tnuts_kernel<Wv, true, true> : bf_tnuts_kernel<Wv, true, false>) : (dec ? bf_tnuts_kernel<Wv, false, true> : bf_tnuts_kernel<Wv, false, false>))
     k = m.DP == 64 ? TN_PICK(4) : (m.DP == 32 ? TN_PICK(2) : TN_PICK(1));
 #undef TN_PICK
-    if (lds > 64 * 1024) BF_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int rc = bf_set_lds(k, lds)) return rc;
     hipLaunchKernelGGL(k, dim3((n_chain + cpg - 1) / cpg), dim3(64 * TN_WAVES), lds, ctx->stream, m, a);
     BF_HIP_CHECK(hipGetLastError());
     return 0;

@@ -864,10 +864,10 @@ static int tg_launch_t(bfhip_ctx *ctx, const TnutsArgs &a, const double *mat) {
     const DevModel &m = ctx->model;
     const TgLds LL = tg_lds_layout(16 * W, m.pld);
     const size_t lds = LL.total * sizeof(double);
-    if (lds > (size_t)160 * 1024)
+    if (lds > BF_LDS_MAX)
         return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_tnuts_run: this pipeline density needs %zu KB of LDS in the tempered kernel (160 KB)", lds / 1024);
     auto k = bf_tnuts_gen_kernel<W, FULLM>;
-    if (lds > 64 * 1024) BF_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int rc = bf_set_lds(k, lds)) return rc;
     hipLaunchKernelGGL(k, dim3((a.n_chain + a.cpg - 1) / a.cpg), dim3(64 * TG_WAVES), lds, ctx->stream, m, a, (double *)mat);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
@@ -879,14 +879,7 @@ int bf_tnuts_gen_launch(bfhip_ctx *ctx, const TnutsArgs &a_in, const double *mat
     const int DP = m.DP;
     // the subtree stack: 4 TN_MAXL vector slots of DP doubles per chain
     const size_t need = (size_t)((a.n_chain + 15) / 16 * 16) * (4 * TN_MAXL) * DP * sizeof(double);
-    if (ctx->scratch_bytes < need) {
-        BF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (ctx->scratch) BF_HIP_CHECK(hipFree(ctx->scratch));
-        ctx->scratch = NULL;
-        ctx->scratch_bytes = 0;
-        BF_HIP_CHECK(hipMalloc(&ctx->scratch, need));
-        ctx->scratch_bytes = need;
-    }
+    if (int rc = bf_grow(ctx, &ctx->scratch, &ctx->scratch_bytes, need)) return rc;
     a.scratch = (double *)ctx->scratch;
     const bool full = mat != NULL;
 #define TG_PICK(Wv) (full ? tg_launch_t<Wv, true>(ctx, a, mat) : tg_launch_t<Wv, false>(ctx, a, mat))
