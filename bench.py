@@ -2,9 +2,15 @@
 """Headline benchmark: leapfrog steps/sec (all chains), 4096 chains x 64-d quadratic surrogate, NUTS -- on SURVEY 8d's
 "Config 3 (headline)": the 64-d rotated banana, round 0 -> one refit cycle -> round 1.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-         bench.py --gpus N --steps K --warmup W
+         bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline needs and nothing else: the workload below, its warm-up and timed launches, --dump-outputs,
+and the JSON line (with the figures taken from those same launches: per-round rates, roofline, refit timings).  --full adds what
+takes runs of its own: the CPU baseline of the headline, the fit timing, the side blocks (tools/benchlib/blocks.py: the other
+configs, the best-case Gaussian, heterogeneous trees, the refit cycle, the other samplers, the config-5 evidence), the layout vote
+of a sharded run and the stored rate of the reference as shipped; --no-cpu-baseline, --no-fit, --no-extras and --no-configs trim it.
 
 A "step" is ONE launch of the fused NUTS kernel that advances every chain of the rank by --iters NUTS iterations (reference
 loop: BaseHMC.run/astep, samplers/hmc_utils/base_hmc.py:62-85,155-156).  The K timed steps are split over the workload's two
@@ -16,9 +22,9 @@ K timed launches (sum of tree_size, samplers/sample_trace.py:529-530; the gradie
 leapfrog step) / the bracketed time of both rounds, max over ranks.  Chains shard over ranks with no data-path collective while
 sampling (weak scaling: 4096 chains per GPU, RNG stream = global chain index); the refit's selection is the path's one exchange.
 
-The CPU baseline is the repository's C restatement of the reference path (oracle/, "port") with its tuned density evaluation, run
-on the host cores on a bounded sample of the same two rounds; it is a reported baseline, never the measured path.  The side
-blocks (tools/benchlib/blocks.py) are never part of `value`.
+The CPU baseline (--full) is the repository's C restatement of the reference path (oracle/, "port") with its tuned density
+evaluation, run on the host cores on a bounded sample of the same two rounds; it is a reported baseline, never the measured path.
+The side blocks are never part of `value`.
 
 --dump-outputs DIR writes what the last of the K timed launches returned (rank 0's samples and stats, float64; a fixed draw of
 the chains when all of them would pass the size cap) to DIR/<name>.npy.  The inputs are fixed by --seed, so two builds run
@@ -105,10 +111,12 @@ def main():
     ap.add_argument('--iters', type=int, default=100, help='NUTS iterations per step = per launch')
     ap.add_argument('--seed', type=int, default=2024)
     ap.add_argument('--backend', default='nccl', help="process-group backend: 'nccl' (= RCCL; default) or 'gloo' (plumbing tests)")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-fit', action='store_true', help='skip the separately reported fit timing')
-    ap.add_argument('--no-extras', action='store_true', help='skip the secondary figures (best-case Gaussian, hetero workload, refit cycle, other samplers)')
-    ap.add_argument('--no-configs', action='store_true', help="skip the blocks on the other BASELINE configs' targets (config2/4/5, DES pipeline, evidence)")
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline, run what takes runs of its own: CPU baselines, fit timing, side blocks, layout vote')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='skip the CPU baselines (of --full and of --workload)')
+    ap.add_argument('--no-fit', action='store_true', help='--full: skip the separately reported fit timing')
+    ap.add_argument('--no-extras', action='store_true', help='--full: skip the secondary figures (best-case Gaussian, hetero workload, refit cycle, other samplers)')
+    ap.add_argument('--no-configs', action='store_true', help="--full: skip the blocks on the other BASELINE configs' targets (config2/4/5, DES pipeline, evidence)")
     ap.add_argument('--workload', default=None, choices=blocks.CONFIG_BLOCKS + ('evidence128', 'gauss64'),
                     help='run ONE block only and print it (profiling: rocprofv3 -- python3 bench.py --workload funnel)')
     ap.add_argument('--dump-outputs', default=None, metavar='DIR',
@@ -180,7 +188,7 @@ def main():
     with torch.cuda.device(ctx.device):
         t_run = time.perf_counter()
         c3 = blocks.config3_rounds(ctx, a.seed, C, a.iters, N_ADAPT_ROUND, k0, a.warmup, rank=rank, world=world, sync=sync,
-                                   cpu_seconds=(14. if (world == 1 and not a.no_cpu_baseline) else 0.), steps_round1=max(k1, 1))
+                                   cpu_seconds=(14. if (world == 1 and a.full and not a.no_cpu_baseline) else 0.), steps_round1=max(k1, 1))
         rounds = c3['rounds']
         if k1 == 0:   # (--steps 1: the line times round 0 alone; round 1 ran one launch for its own block)
             timed_rounds = rounds[:1]
@@ -201,7 +209,7 @@ def main():
         # the layout vote of a sharded run (DeviceChains._note_trees: the histogram of a launch's tree sizes summed over the ranks, so
         # that every rank chooses the same layout for the next launch) is INSIDE the timed launches above; its own cost, for the record
         vote = None
-        if dist is not None:
+        if dist is not None and a.full:
             from bayesfast_amd import parallel, _lib
             from bayesfast_amd.chains import DeviceChains
             st = ctx.zeros((C, a.iters, _lib.STAT_STRIDE))
@@ -274,16 +282,17 @@ def main():
             out['layout_vote'] = vote
         if 'cpu_baseline' in c3:
             out['cpu_baseline'] = c3['cpu_baseline']
-        elif not a.no_cpu_baseline:
+        elif a.full and not a.no_cpu_baseline:
             out['cpu_baseline'] = None
-        try:   # the AS-SHIPPED reference's rate: a stored measurement of the build container (tools/time_reference.py), never timed here
-            rt = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'reference_timing.json')))
-            out['reference_as_shipped'] = {'leapfrog_steps_per_sec_per_core': rt['leapfrog_steps_per_sec_per_core'],
-                                           'polymodel_fit_s': rt.get('polymodel_fit_s'), 'host': rt['host']['cpu'],
-                                           'source': 'tests/golden/reference_timing.json (build container; the Python reference does not travel)'}
-        except Exception:
-            pass
-        if world == 1:
+        if a.full:
+            try:   # the AS-SHIPPED reference's rate: a stored measurement on a CPU host (tools/time_reference.py), never timed here
+                rt = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'reference_timing.json')))
+                out['reference_as_shipped'] = {'leapfrog_steps_per_sec_per_core': rt['leapfrog_steps_per_sec_per_core'],
+                                               'polymodel_fit_s': rt.get('polymodel_fit_s'), 'host': rt['host']['cpu'],
+                                               'source': 'tests/golden/reference_timing.json (stored; the Python reference is not run here)'}
+            except Exception:
+                pass
+        if world == 1 and a.full:
             from bayesfast_amd.workloads import correlated_gaussian_spec
             _, cov = correlated_gaussian_spec(d)
             with torch.cuda.device(ctx.device):

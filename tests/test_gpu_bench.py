@@ -11,6 +11,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
         'vs_baseline', 'dtype', 'data', 'config', 'roofline')
+FULL_ONLY = ('cpu_baseline', 'fit', 'gauss64_best_case', 'hetero', 'scaled_inputs', 'refit_cycle', 'full_metric', 'tempered', 'config2',
+             'config4', 'config5', 'pipeline_des', 'config5_evidence', 'reference_as_shipped', 'layout_vote', 'extras_error')
 
 
 def _line(out):
@@ -20,7 +22,7 @@ def _line(out):
 
 
 def test_bench_single_gpu_line():
-    r = subprocess.run([sys.executable, 'bench.py', '--steps', '2', '--warmup', '2', '--chains', '512', '--no-cpu-baseline', '--no-configs'],
+    r = subprocess.run([sys.executable, 'bench.py', '--steps', '2', '--warmup', '2', '--chains', '512', '--full', '--no-cpu-baseline', '--no-configs'],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _line(r.stdout)
@@ -48,6 +50,20 @@ def test_bench_single_gpu_line():
     assert j['gauss64_best_case']['value'] > 0
 
 
+def test_bench_plain_run_is_lean():
+    """Without --full the run is the headline alone: the line carries the figures of its own launches and none of what takes
+    runs of its own (CPU baselines, fit timing, side blocks, the stored reference rate)."""
+    r = subprocess.run([sys.executable, 'bench.py', '--steps', '2', '--warmup', '1', '--chains', '256'],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = _line(r.stdout)
+    for k in KEYS + ('config3_round0', 'config3_round1', 'refit'):
+        assert k in j, k
+    assert j['steps'] == 2 and j['warmup'] == 1 and j['value'] > 0 and j['config']['chains_per_gpu'] == 256
+    for k in FULL_ONLY:
+        assert k not in j, k
+
+
 def test_bench_dump_outputs(tmp_path):
     """--dump-outputs DIR: the samples and stats of the line's last timed launch (round 1's with --steps 2), float64, every chain
     when they fit the size cap; their trees are the leapfrogs the line counts for that launch."""
@@ -69,7 +85,7 @@ def test_bench_two_ranks_on_one_gpu_gloo():
     port = 29700 + os.getpid() % 200
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(port), 'bench.py', '--gpus', '2', '--steps', '2', '--warmup', '2', '--chains', '256',
-           '--backend', 'gloo', '--no-cpu-baseline']
+           '--backend', 'gloo', '--full', '--no-cpu-baseline']
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     j = _line(r.stdout)
@@ -90,7 +106,7 @@ def test_bench_four_ranks_rehearsal_on_one_gpu_gloo():
     port = 29300 + os.getpid() % 150
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '4', '--master-addr', '127.0.0.1',
            '--master-port', str(port), 'bench.py', '--gpus', '4', '--steps', '1', '--warmup', '1', '--chains', '128',
-           '--backend', 'gloo', '--no-cpu-baseline']
+           '--backend', 'gloo', '--full', '--no-cpu-baseline']
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     j = _line(r.stdout)
