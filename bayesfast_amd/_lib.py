@@ -112,7 +112,10 @@ SYMBOLS = {
     'bfhip_bridge_sums': (C.c_int, [_vp, C.c_long, _vp, C.c_long, _vp, C.c_double, _vp]),
     'bfhip_bridge_terms': (C.c_int, [_vp, C.c_long, _vp, _vp, C.c_long, _vp, _vp, C.c_double, _vp, _vp]),
     'bfhip_logmeanexp_stats': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp]),
+    'bfhip_acor_moments': (C.c_int, [_vp, C.c_int, C.c_long, C.c_int, C.c_long, _vp, _vp, _vp]),
+    'bfhip_acor_lag_sums': (C.c_int, [_vp, C.c_int, C.c_long, C.c_int, C.c_long, _vp, _vp, _vp, C.c_long, C.c_int, _vp, _vp]),
 }
+ACOR_MAX_GROUPS = 256   # walker groups of bfhip_acor_lag_sums: its work buffer is min(n_w, 256) * n_lag * n_d doubles
 
 _lib = None
 

@@ -389,6 +389,37 @@ class TraceTuple:
 
     __call__ = get
 
+    def integrated_time(self, since_iter=None, include_warmup=False, original_space=True, return_type='samples', c=5, tol=50,
+                        quiet=False):
+        """The integrated autocorrelation time (n_d,) of the chains (``bayesfast_amd.utils.integrated_time``) over what
+        ``get(since_iter, include_warmup, original_space, return_type, flatten=False)`` selects, without materialising it: the
+        device route reads this rank's shard in place (``return_type='logp'`` in the sampler's space: a small contiguous copy of
+        the logp column, n_d = 1).  Under ``torch.distributed`` with more than one rank a collective, to be called by every
+        rank; every rank gets the same tau and only lag sums cross between ranks (no ``gather()``)."""
+        from .. import parallel
+        from ..utils import acor
+        if since_iter is None:
+            since_iter = 0 if include_warmup else self.n_warmup
+        since_iter = int(since_iter)
+        if since_iter >= self.i_iter - 1:
+            raise ValueError('since_iter is too large. Nothing to return.')
+        if return_type == 'samples':
+            x = self._parts['samples_original' if original_space else 'samples'][:, since_iter:]
+        elif return_type == 'logp':
+            if original_space:
+                x = self._parts['logp_original'][:, since_iter:, None]
+            else:
+                x = self._parts['stats'][:, since_iter:, 0:1]
+                x = x.contiguous() if hasattr(x, 'contiguous') else np.ascontiguousarray(x)
+        else:
+            raise ValueError('invalid value for return_type.')
+        if parallel.world()[1] == 1 and not getattr(x, 'is_cuda', False):
+            return acor.integrated_time(np.asarray(x), c, tol, quiet)      # host parts: the host port
+        if not hasattr(x, 'is_cuda'):
+            import torch
+            x = torch.as_tensor(x)
+        return acor.integrated_time_sharded(x, self.n_chain, c, tol, quiet)
+
     def __getitem__(self, key):
         return self.sample_traces[key]
 

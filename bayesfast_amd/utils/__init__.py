@@ -1,3 +1,4 @@
+from .acor import integrated_time, AutocorrError
 from .resample import SystematicResampler
 
-__all__ = ['SystematicResampler']
+__all__ = ['SystematicResampler', 'integrated_time', 'AutocorrError']

@@ -37,7 +37,8 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_DIM 128         /* input_size limit of the device path */
 #define BFHIP_MAX_TREEDEPTH 12
 
-/* 102 (round 6): bfhip_polar_ns takes 2 d^2 + n_iter + 10 doubles of work.  101 (round 6): BFHIP_TREE_MODE_WORK grew to 4162 and
+/* 103: bfhip_acor_moments and bfhip_acor_lag_sums, the device integrated autocorrelation time.  102 (round 6): bfhip_polar_ns
+ * takes 2 d^2 + n_iter + 10 doubles of work.  101 (round 6): BFHIP_TREE_MODE_WORK grew to 4162 and
  * work[0] of bfhip_tree_size_mode_share carries the laggard bit; 100 before. */
 int bfhip_version(void);
 const char *bfhip_last_error(void);
@@ -463,6 +464,23 @@ int bfhip_ica_post(bfhip_ctx *ctx, int d, const double *w1, double *w, const dou
  * in the caller's memory, so that a HIP graph holding the launch stays valid); resid (1,) receives max |x x^T - I| (device memory:
  * nothing synchronises; a caller checks it when it next looks at the device).  d <= 1024. */
 int bfhip_polar_ns(bfhip_ctx *ctx, int d, const double *a, double *x, int n_iter, double *work, double *resid);
+
+/* The integrated autocorrelation time of many chains (utils/acor.py:79-145, integrated_time: emcee's estimator with Sokal's
+ * automatic window; the reference's PostStep calls it, core/recipe.py:1304): the two reductions over walkers and time behind it.
+ * x: n_w walkers of (n_t, n_d) float64 each, walker w at x + w ldw (ldw >= n_t n_d, so that samples[:, since:] goes in as it is),
+ * every walker's block row-major and contiguous.  y_wk(s) = x_wk(s) - mean_wk, a_wk(t) = sum_{s < n_t - t} y_wk(s) y_wk(s + t).
+ *   bfhip_acor_moments   mean (n_w, n_d) <- mean_wk; inv (n_w, n_d) <- 1 / a_wk(0), both by two passes over time (a constant series
+ *                        has inv = inf, and its lag sums are NaN, as the host port's 0 / 0)
+ *   bfhip_acor_lag_sums  out (n_lag, n_d) <- sum_w a_wk(t0 + i) inv_wk for i < n_lag (0 for lags >= n_t); mean and inv from
+ *                        bfhip_acor_moments.  work: min(n_w, 256) n_lag n_d doubles (per-walker-group partial sums).
+ * The window search (rho_k = out / n_w, tau_k(t) = 2 sum rho_k - 1, the first t >= c tau_k(t)) is the caller's: it asks for lag
+ * blocks until every window has closed.  n_d >= 1 of any size (BFHIP_MAX_DIM does not apply); NaN propagates.  Every sum has a
+ * fixed order set by (n_w, n_t, n_d) alone: bitwise repeatable, and a lag's sum does not depend on the block that computes it.
+ * Work: n_w n_t n_d reads twice (moments); n_w n_d n_lag (n_t - t0) FMAs and n_w n_t n_d reads per 64 lags (lag sums).
+ * Stream-ordered, no host synchronisation. */
+int bfhip_acor_moments(bfhip_ctx *ctx, int n_w, long n_t, int n_d, long ldw, const double *x, double *mean, double *inv);
+int bfhip_acor_lag_sums(bfhip_ctx *ctx, int n_w, long n_t, int n_d, long ldw, const double *x, const double *mean, const double *inv,
+                        long t0, int n_lag, double *work, double *out);
 
 /* NOT part of this interface: the library's test and tuning switches (force a chain layout, a kernel form or a chains-per-workgroup
  * count; attach measurement buffers; run a launch in one part).  They have ONE entry point each for integers and for buffers,
