@@ -67,6 +67,10 @@ class PipelineDesc(C.Structure):  # bfhip_pipeline_desc
                 ('decay_gamma', C.c_double)]
 
 
+class LaplaceOpts(C.Structure):  # bfhip_laplace_opts
+    _fields_ = [('max_iter', C.c_int), ('xtol', C.c_double)]
+
+
 # every symbol include/bfhip.h declares: (restype, argtypes)
 _vp = C.c_void_p
 SYMBOLS = {
@@ -114,6 +118,8 @@ SYMBOLS = {
     'bfhip_logmeanexp_stats': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp]),
     'bfhip_acor_moments': (C.c_int, [_vp, C.c_int, C.c_long, C.c_int, C.c_long, _vp, _vp, _vp]),
     'bfhip_acor_lag_sums': (C.c_int, [_vp, C.c_int, C.c_long, C.c_int, C.c_long, _vp, _vp, _vp, C.c_long, C.c_int, _vp, _vp]),
+    'bfhip_logp_hess': (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
+    'bfhip_laplace_opt': (C.c_int, [_vp, C.POINTER(LaplaceOpts), C.c_int, _vp, _vp, _vp, _vp, _vp]),
 }
 ACOR_MAX_GROUPS = 256   # walker groups of bfhip_acor_lag_sums: its work buffer is min(n_w, 256) * n_lag * n_d doubles
 

@@ -248,6 +248,13 @@ class SurrogateDensity:
     def grad(self, x, original_space=True):
         return self.logp_and_grad(x, original_space)[1]
 
+    def hess(self, x, original_space=True):
+        """The analytic Hessian of ``logp`` at x (d,) or (n, d): (d, d) or (n, d, d), symmetric (``DeviceDensity.logp_grad_hess``).
+        Where the decay term is on in the sampling space it is the symmetric part of the gradient's Jacobian (the reference's
+        decay gradient carries no transform Jacobian, core/density.py:745)."""
+        x = np.asarray(x, dtype=np.float64)
+        return self.device().logp_grad_hess(x, original_space)[2].cpu().numpy()
+
 
 class Chi2PipelineDensity(SurrogateDensity):
     """A pipeline evaluated AND sampled on the device: a multi-output ``PolyModel`` surrogate (x -> m outputs), a Gaussian

@@ -368,6 +368,41 @@ class DeviceDensity:
                                                  _ptr(logp), _ptr(grad)))
         return (logp[0], grad[0]) if single else (logp, grad)
 
+    def logp_grad_hess(self, x, original_space=False):
+        """x: (n, d) or (d,) -> (logp (n,), grad (n, d), hess (n, d, d)) float64 device tensors: the analytic Hessian of the
+        function ``logp_and_grad`` returns (``bfhip_logp_hess``), symmetric bit for bit.  A pipeline density (a spec with a
+        ``'chi2'`` stage) raises NotImplementedError: difference its gradient instead (``utils.laplace``)."""
+        torch = _torch()
+        self.upload_if_needed()
+        xt = self.ctx.tensor(x, torch.float64)
+        single = xt.dim() == 1
+        xt = xt.reshape(-1, self.d)
+        n = xt.shape[0]
+        logp = self.ctx.empty((n,))
+        grad = self.ctx.empty((n, self.d))
+        hess = self.ctx.empty((n, self.d, self.d))
+        _lib.check(self.ctx._lib.bfhip_logp_hess(self.ctx.handle, n, _ptr(xt), int(bool(original_space)), _ptr(logp), _ptr(grad),
+                                                 _ptr(hess)))
+        return (logp[0], grad[0], hess[0]) if single else (logp, grad, hess)
+
+    MAXIMIZE_STATUS = ('converged', 'max_iter reached', 'non-finite logp', 'the last step was short but damped')
+
+    def maximize(self, x0, max_iter=200, xtol=1e-5):
+        """Damped Newton maximisation of logp in the sampling space from every row of x0 (n_start, d) or (d,), all starts in one
+        launch (``bfhip_laplace_opt``, a workgroup per start).  Returns a dict of float64 device tensors: ``x`` (n_start, d),
+        ``logp`` (n_start,), ``hess`` (n_start, d, d) at x, ``info`` (n_start, 4) = accepted iterations, status (index into
+        ``MAXIMIZE_STATUS``), the last mean |step|, the last damping lambda."""
+        torch = _torch()
+        self.upload_if_needed()
+        xt = self.ctx.tensor(x0, torch.float64).reshape(-1, self.d)
+        n = xt.shape[0]
+        out = dict(x=self.ctx.empty((n, self.d)), logp=self.ctx.empty((n,)), hess=self.ctx.empty((n, self.d, self.d)),
+                   info=self.ctx.empty((n, 4)))
+        opts = _lib.LaplaceOpts(int(max_iter), float(xtol))
+        _lib.check(self.ctx._lib.bfhip_laplace_opt(self.ctx.handle, C.byref(opts), n, _ptr(xt), _ptr(out['x']), _ptr(out['logp']),
+                                                   _ptr(out['hess']), _ptr(out['info'])))
+        return out
+
     _WHICH = {'from_original': 0, 'from_original_grad': 1, 'from_original_grad2': 2, 'to_original': 3,
               'to_original_grad': 4, 'to_original_grad2': 5}
 

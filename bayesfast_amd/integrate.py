@@ -20,6 +20,10 @@ reference's classes (the bases are taken from the imported package at call time;
 * ``sample``           the signature of ``bayesfast.core.sample.sample``: takes the reference's ``Density`` (read by duck
                        typing, ``adapters.py``) and the reference's ``NTrace`` / ``HTrace`` / dict / a ``TraceTuple`` returned
                        earlier (continue the chains), runs all chains in fused device launches.
+* ``Laplace``          subclass of ``bayesfast.utils.laplace.Laplace``: the reference's constructor and checks (inherited); ``run``
+                       goes through ``bayesfast_amd.utils.Laplace`` -- the device's Newton maximiser on the analytic Hessian when
+                       the density reaches it (``patch(..., laplace=True)``), scipy with one-launch differences otherwise -- and
+                       returns the reference's ``LaplaceResult``.  ``OptimizeStep(laplace=...)`` accepts it.
 * ``patch(bayesfast)`` rebinds ``sample`` where ``Recipe`` looks it up (``bayesfast.core.recipe.sample``) and at the
                        package's public names, and ``PolyModel`` at ``bayesfast.modules`` / ``bayesfast``; returns a
                        callable that undoes it.
@@ -32,7 +36,7 @@ import copy
 
 import numpy as np
 
-__all__ = ['reference_classes', 'PolyModel', 'GaussianLikelihood', 'GaussianPrior', 'GaussianBaseDensity', 'sample', 'patch', 'as_surrogate_density']
+__all__ = ['reference_classes', 'PolyModel', 'Laplace', 'GaussianLikelihood', 'GaussianPrior', 'GaussianBaseDensity', 'sample', 'patch', 'as_surrogate_density']
 
 _CLASSES = {}
 
@@ -305,7 +309,23 @@ def reference_classes(bayesfast=None):
                 t._stats = cls()._fill(inner._stats[i], inner.n_warmup)
             return t
 
-    ns = SimpleNamespace(bayesfast=bf, PolyModel=PolyModel, GaussianLikelihood=GaussianLikelihood, GaussianPrior=GaussianPrior,
+    ref_laplace = bf.utils.laplace
+
+    class Laplace(ref_laplace.Laplace):
+        __doc__ = ("``bayesfast.utils.laplace.Laplace`` (utils/laplace.py:17-205) whose ``run`` needs no ``numdifftools``: the "
+                   "constructor, its checks and ``untemper_laplace_samples`` are the reference's own; ``run`` is "
+                   "``bayesfast_amd.utils.Laplace.run`` with the same settings.  Inside ``Recipe._opt_surro`` under "
+                   "``patch(..., laplace=True)`` the recipe's density is maximised on the device (all of it in one launch).")
+
+        def run(self, logp, x_0, grad=None, hess=None):
+            from .utils import laplace as ours
+            lap = ours.Laplace(self._optimize_method, self._optimize_tol, self._optimize_options, self._max_cond, self._n_sample,
+                               self._beta, self._mvn_generator, self._grad_options, self._hess_options)
+            den = ours.get_current_density()
+            res = lap.run(den, x_0) if den is not None else lap.run(logp, x_0, grad, hess)
+            return ref_laplace.LaplaceResult(*res)   # (the type the reference's untemper_laplace_samples asks for)
+
+    ns = SimpleNamespace(bayesfast=bf, PolyModel=PolyModel, Laplace=Laplace, GaussianLikelihood=GaussianLikelihood, GaussianPrior=GaussianPrior,
                          GaussianBaseDensity=GaussianBaseDensity, TraceTuple=TraceTuple,
                          _our_st=_our_st)
     _CLASSES[id(bf)] = ns
@@ -315,6 +335,11 @@ def reference_classes(bayesfast=None):
 def PolyModel(*args, **kwargs):
     """``reference_classes().PolyModel(...)``: a reference ``PolyModel`` (it IS one) that fits on the GPU."""
     return reference_classes().PolyModel(*args, **kwargs)
+
+
+def Laplace(*args, **kwargs):
+    """``reference_classes().Laplace(...)``: a reference ``Laplace`` (it IS one) that runs without ``numdifftools``."""
+    return reference_classes().Laplace(*args, **kwargs)
 
 
 def GaussianLikelihood(*args, **kwargs):
@@ -523,11 +548,16 @@ def sample(density, sample_trace=None, sampler='NUTS', n_run=None, parallel_back
     return ns.TraceTuple(inner, sample_trace)
 
 
-def patch(bayesfast=None, fallback=False):
+def patch(bayesfast=None, fallback=False, laplace=False):
     """Rebind the reference's names to the device path: ``bayesfast.core.recipe.sample`` (what ``Recipe`` calls),
     ``bayesfast.core.sample.sample``, ``bayesfast.core.sample`` / ``bayesfast.sample`` where they name the function, and
     ``PolyModel`` at ``bayesfast.modules.poly`` / ``bayesfast.modules`` / ``bayesfast.core.recipe`` / ``bayesfast``.
     ``fallback=True``: densities the device path does not cover go to the reference's own sampler instead of raising.
+    ``laplace=True``: the OptimizeStep's Laplace approximation runs on the device too -- ``Laplace`` at
+    ``bayesfast.core.recipe`` / ``bayesfast.utils.laplace`` / ``bayesfast.utils`` becomes the seam's subclass (so an
+    ``OptimizeStep`` built afterwards holds one), and ``Recipe._opt_surro`` is wrapped so that, for its duration, the recipe's
+    density -- where ``as_surrogate_density`` covers it -- is what that subclass's ``run`` maximises, instead of the lambdas the
+    recipe passes.  The default leaves the OptimizeStep exactly as the reference runs it.
     Returns ``unpatch()``."""
     ns = reference_classes(bayesfast)
     bf = ns.bayesfast
@@ -561,6 +591,33 @@ def patch(bayesfast=None, fallback=False):
     for obj in (sys.modules[bf.__name__ + '.modules.poly'], bf.modules, recipe_module, bf):
         if getattr(obj, 'PolyModel', None) is ref_poly:
             rebind(obj, 'PolyModel', ns.PolyModel)
+
+    if laplace:
+        ref_lap = sys.modules[bf.__name__ + '.utils.laplace'].Laplace
+        for obj in (sys.modules[bf.__name__ + '.utils.laplace'], bf.utils, recipe_module):
+            if getattr(obj, 'Laplace', None) is ref_lap:
+                rebind(obj, 'Laplace', ns.Laplace)
+        original_opt_surro = recipe_module.Recipe._opt_surro
+
+        def _opt_surro(self, x_0, var_dicts):
+            from .utils import laplace as ours
+            den = None
+            if isinstance(self.recipe_trace._s_optimize.laplace, ns.Laplace):
+                # (the recipe asks for use_surrogate=True per call, core/recipe.py:803-806; the flag itself is off while it fits)
+                flag = self.density.use_surrogate
+                self.density.use_surrogate = True
+                try:
+                    den = as_surrogate_density(self.density)
+                    if den.spec().get('chi2') is not None:   # (the pipeline density: the host route, through the recipe's lambdas)
+                        den = None
+                except NotImplementedError:
+                    den = None
+                finally:
+                    self.density.use_surrogate = flag
+            with ours.current_density(den):
+                return original_opt_surro(self, x_0, var_dicts)
+
+        rebind(recipe_module.Recipe, '_opt_surro', _opt_surro)
 
     def unpatch():
         while saved:

@@ -1,4 +1,5 @@
 from .acor import integrated_time, AutocorrError
 from .resample import SystematicResampler
+from .laplace import Laplace, LaplaceResult, make_positive
 
-__all__ = ['SystematicResampler', 'integrated_time', 'AutocorrError']
+__all__ = ['SystematicResampler', 'integrated_time', 'AutocorrError', 'Laplace', 'LaplaceResult', 'make_positive']

@@ -37,7 +37,8 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_DIM 128         /* input_size limit of the device path */
 #define BFHIP_MAX_TREEDEPTH 12
 
-/* 103: bfhip_acor_moments and bfhip_acor_lag_sums, the device integrated autocorrelation time.  102 (round 6): bfhip_polar_ns
+/* 104: bfhip_logp_hess and bfhip_laplace_opt, the analytic Hessian of the surrogate density and the device Newton maximiser.
+ * 103: bfhip_acor_moments and bfhip_acor_lag_sums, the device integrated autocorrelation time.  102 (round 6): bfhip_polar_ns
  * takes 2 d^2 + n_iter + 10 doubles of work.  101 (round 6): BFHIP_TREE_MODE_WORK grew to 4162 and
  * work[0] of bfhip_tree_size_mode_share carries the laggard bit; 100 before. */
 int bfhip_version(void);
@@ -481,6 +482,35 @@ int bfhip_polar_ns(bfhip_ctx *ctx, int d, const double *a, double *x, int n_iter
 int bfhip_acor_moments(bfhip_ctx *ctx, int n_w, long n_t, int n_d, long ldw, const double *x, double *mean, double *inv);
 int bfhip_acor_lag_sums(bfhip_ctx *ctx, int n_w, long n_t, int n_d, long ldw, const double *x, const double *mean, const double *inv,
                         long t0, int n_lag, double *work, double *out);
+
+/* The OptimizeStep's Laplace approximation (utils/laplace.py:131-183; the reference differences the gradient with numdifftools, at
+ * every Newton-CG iteration and once more at the maximum, one point per call).  Both calls take the uploaded SCALAR surrogate density
+ * with every feature of bfhip_density_desc; a pipeline density (bfhip_pipeline_upload) is refused with BFHIP_ERR_UNSUPPORTED.
+ *
+ * bfhip_logp_hess: Density.logp / grad and the Hessian of logp for n points: x (n,d) -> logp (n,), grad (n,d) (either may be NULL),
+ * hess (n,d,d) row-major.  The Hessian is the closed form of the function bfhip_logp_grad returns -- polynomial, surrogate input
+ * scaling, the linear extrapolation outside the bound, the decay term, the Gaussian link, the constraint transform when
+ * original_space = 0 -- i.e. the symmetrised Jacobian of that gradient, symmetric bit for bit.  On the surfaces beta = alpha and
+ * beta_d^2 = alpha_2, where the function is only C^1, it takes the branch the gradient takes.  A workgroup per point.  The output is
+ * 8 n d^2 bytes; the kernel is NOT bound by those stores but by the evaluation in front of them (measured: docs/EXPERIMENTS.md).
+ * Stream-ordered, no host synchronisation. */
+int bfhip_logp_hess(bfhip_ctx *ctx, int n, const double *x, int original_space, double *logp, double *grad, double *hess);
+
+typedef struct {
+    int max_iter;   /* accepted steps per start */
+    double xtol;    /* mean |step| <= xtol ends a start, as Newton-CG's avextol does */
+} bfhip_laplace_opts;
+
+/* n_start independent maximisations of the uploaded density in the sampling space (original_space = 0), one workgroup each, the
+ * whole iteration inside one launch: Newton steps (-H + lambda I) s = g by a Cholesky factorisation in LDS, lambda = 0 tried first in
+ * every iteration and raised tenfold (Levenberg) while the matrix does not factor or the step does not increase logp.
+ * x0 (n_start,d) -> x (n_start,d), logp (n_start,), hess (n_start,d,d) at x (may be NULL), info (n_start,4) doubles: accepted
+ * iterations; status (0 converged: mean |step| <= xtol on an UNDAMPED step, lambda = 0; 1 max_iter; 2 non-finite logp or step;
+ * 3 step <= xtol but still damped, e.g. a singular Hessian); the last mean |step|; the last lambda.
+ * A start's result depends on its x0 row and the density only -- not on n_start, nor on the workgroup that ran it.
+ * Stream-ordered, no host synchronisation. */
+int bfhip_laplace_opt(bfhip_ctx *ctx, const bfhip_laplace_opts *opts, int n_start, const double *x0, double *x, double *logp,
+                      double *hess, double *info);
 
 /* NOT part of this interface: the library's test and tuning switches (force a chain layout, a kernel form or a chains-per-workgroup
  * count; attach measurement buffers; run a launch in one part).  They have ONE entry point each for integers and for buffers,

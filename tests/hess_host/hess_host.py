@@ -1,0 +1,50 @@
+"""ctypes front end of ``bayesfast_amd/csrc/bfhip_hess.h`` compiled for the host (TEST INFRASTRUCTURE ONLY): the analytic Hessian
+and the damped Newton maximiser of the device kernels, run by one host thread on the tables the upload builds.  Nothing under
+``bayesfast_amd/`` imports this module."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        subprocess.check_call(['make', '-C', _HERE, '-s'])
+        _lib = C.CDLL(os.path.join(_HERE, '_build', 'libbf_hess_host.so'))
+    return _lib
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def logp_grad_hess(spec, x, original_space=False):
+    """x (n, d) -> logp (n,), grad (n, d), hess (n, d, d) of the spec's surrogate density, by the header's arithmetic."""
+    from bayesfast_amd.device import density_desc_from_spec
+    ds, keep = density_desc_from_spec(spec)
+    x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+    n, d = x.shape
+    logp, grad, hess = np.empty(n), np.empty((n, d)), np.empty((n, d, d))
+    rc = lib().bfhost_logp_hess(C.byref(ds), C.c_int(n), _p(x), C.c_int(int(bool(original_space))), _p(logp), _p(grad), _p(hess))
+    if rc != 0:
+        raise RuntimeError('bfhost_logp_hess failed: %d' % rc)
+    return logp, grad, hess
+
+
+def maximize(spec, x0, max_iter=200, xtol=1e-5):
+    """x0 (n_start, d) -> x, logp, hess, info as ``bfhip_laplace_opt`` returns them."""
+    from bayesfast_amd.device import density_desc_from_spec
+    ds, keep = density_desc_from_spec(spec)
+    x0 = np.ascontiguousarray(np.atleast_2d(x0), dtype=np.float64)
+    n, d = x0.shape
+    x, logp, hess, info = np.empty((n, d)), np.empty(n), np.empty((n, d, d)), np.empty((n, 4))
+    rc = lib().bfhost_laplace_opt(C.byref(ds), C.c_int(int(max_iter)), C.c_double(float(xtol)), C.c_int(n), _p(x0), _p(x), _p(logp),
+                                  _p(hess), _p(info))
+    if rc != 0:
+        raise RuntimeError('bfhost_laplace_opt failed: %d' % rc)
+    return x, logp, hess, info
