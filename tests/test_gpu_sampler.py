@@ -815,9 +815,10 @@ def test_config1_donut_shapes_2d_decay_no_bound(ctx, order):
 
 def test_tree_size_mode_share_flag_matches_numpy(ctx):
     """bfhip_tree_size_mode_share (the layout choice's helper): the most common tree_size of the given rows when its share
-    >= threshold, else 0, for uniform, mixed and out-of-range sizes; the work buffer is left clean between calls."""
+    >= threshold, else 0, for uniform, mixed and out-of-range sizes; the work buffer is left clean between calls.  The host
+    restatement that chains sharded over ranks use (layout.answer_from_histograms) gives the same integer from the window's histograms."""
     import torch
-    from bayesfast_amd import _lib
+    from bayesfast_amd import _lib, layout
     from bayesfast_amd.device import _ptr
     rng = np.random.default_rng(8)
     n_chain, n_out = 300, 40
@@ -847,6 +848,9 @@ def test_tree_size_mode_share_flag_matches_numpy(ctx):
         torch.cuda.synchronize()
         w = work.cpu().numpy()
         assert int(w[0]) == want, (p_mode, row0, n_rows, slow, int(w[0]), want)
+        cls = np.clip(np.searchsorted(np.array(_lib.LAG_EDGES), sums, side='right') - 1, 0, 63)   # (as DeviceChains._note_trees bins them)
+        hists = np.bincount(blk, minlength=4096).tolist(), np.bincount(cls, minlength=64).tolist()
+        assert layout.answer_from_histograms(*hists, float(share)) == int(w[0]), (p_mode, row0, n_rows, slow)
         assert not w[1:].any()  # histograms and arrival counter cleared for the next call
         seen.add(((want & 4095) > 0, want >= 4096))
     assert seen >= {(True, False), (True, True), (False, True)}   # (in step without and with a laggard; a laggard among trees that differ)
@@ -950,7 +954,7 @@ def test_config5_four_wave_form_is_bit_identical_to_the_eight_wave_form(ctx, n_c
 
 
 def test_auto_layout_takes_the_wave_kernel_for_deep_trees_with_the_decay_term(ctx):
-    """chains._deep_trees_prefer_waves: the common surrogate with the decay term at d = 64, trees in step -- 'auto' runs the group
+    """layout.deep_trees_prefer_waves: the common surrogate with the decay term at d = 64, trees in step -- 'auto' runs the group
     kernel while the trees have 7 leaves and the pipelined wave-per-chain kernel once they have 31 (the helper of the layout vote
     reports the common tree size); the module's layout, forced, gives the same trees and moments (forced 'split' runs the group
     kernel here: there is no split instantiation with the decay term)."""
@@ -985,7 +989,7 @@ def test_auto_layout_takes_the_wave_kernel_for_deep_trees_with_the_decay_term(ct
 
 
 def test_auto_layout_runs_two_groups_per_cu_in_the_group_kernel_at_d32(ctx):
-    """chains._two_groups_fit_a_cu: 32 chains per CU at 17 <= d <= 32 with the trees in step -- 'auto' runs the group kernel (two
+    """layout.two_groups_fit_a_cu: 32 chains per CU at 17 <= d <= 32 with the trees in step -- 'auto' runs the group kernel (two
     workgroups per CU, a wave per SIMD) where it ran the split kernel (one).  Against the module's layout, forced: the group and
     the split kernel give the same results bit for bit, the wave layout the same trees and moments (it agrees to rounding)."""
     from bayesfast_amd.device import DeviceDensity

@@ -376,32 +376,34 @@ def test_blas_single_thread_context_limits_and_restores():
 
 
 def test_layout_rules_are_functions_of_the_shapes_only():
-    """DeviceChains' shape rules for the automatic layout (tools/dispatch_sweep.py measured them): the wave layout for few chains,
-    up to eight per CU with the decay term or the constraint transform (the pipelined kernel's feature sets), never for both
+    """The shape rules of the automatic layout (bayesfast_amd/layout.py; tools/dispatch_sweep.py measured them): the wave layout for few
+    chains, up to eight per CU with the decay term or the constraint transform (the pipelined kernel's feature sets), never for both
     together or for other densities; the lane layouts whatever the trees at d <= 32 from sixteen chains per CU."""
-    import types
-    from bayesfast_amd.chains import DeviceChains
+    from bayesfast_amd import layout
 
-    def stub(d, n, spec_extra=None, configs=('linear', 'quadratic'), n_rule=None, full=False):
+    def facts(d, n, spec_extra=None, configs=('linear', 'quadratic'), n_rule=None, full=False):
         sp = dict(poly=dict(use_bound=True, configs=[dict(order=o) for o in configs]), **(spec_extra or {}))
-        o = types.SimpleNamespace(density=types.SimpleNamespace(spec=sp), d=d, n_chain=n, n_chain_rule=n_rule, full_metric=full, _n_cu=256, ctx=None)
-        for name in ('_shape_facts', '_small_problem', '_lanes_whatever_the_trees'):
-            setattr(o, name, types.MethodType(getattr(DeviceChains, name), o))
-        return o
+        return layout.shape_facts(sp, d, n, 256, full, n_rule)
+
+    def small(*a, **k):
+        return layout.small_problem(facts(*a, **k))
+
+    def lanes(*a, **k):
+        return layout.lanes_whatever_the_trees(facts(*a, **k))
 
     dec = dict(use_decay=True)
     tr = dict(ranges=np.zeros((64, 2)))
-    assert stub(64, 1024)._small_problem() and not stub(64, 2048)._small_problem()
-    assert stub(32, 1024)._small_problem() and not stub(32, 2048)._small_problem()
-    assert stub(64, 2048, dec)._small_problem() and not stub(64, 4096, dec)._small_problem()
-    assert stub(32, 2048, tr)._small_problem() and not stub(32, 4096, tr)._small_problem()
-    assert not stub(64, 512, dict(dec, **tr))._small_problem()                      # no pipelined instantiation with both
-    assert not stub(64, 512, configs=('linear', 'quadratic', 'cubic-2'))._small_problem()
-    assert not stub(64, 512, dec, full=True)._small_problem()
-    assert stub(64, 16384, dec, n_rule=2048)._small_problem()                       # sharded: chains per rank
-    assert stub(16, 4096)._lanes_whatever_the_trees() and stub(32, 8192)._lanes_whatever_the_trees()
-    assert not stub(32, 2048)._lanes_whatever_the_trees() and not stub(64, 4096)._lanes_whatever_the_trees()
-    assert not stub(16, 4096, dec)._lanes_whatever_the_trees()
+    assert small(64, 1024) and not small(64, 2048)
+    assert small(32, 1024) and not small(32, 2048)
+    assert small(64, 2048, dec) and not small(64, 4096, dec)
+    assert small(32, 2048, tr) and not small(32, 4096, tr)
+    assert not small(64, 512, dict(dec, **tr))                      # no pipelined instantiation with both
+    assert not small(64, 512, configs=('linear', 'quadratic', 'cubic-2'))
+    assert not small(64, 512, dec, full=True)
+    assert small(64, 16384, dec, n_rule=2048)                       # sharded: chains per rank
+    assert lanes(16, 4096) and lanes(32, 8192)
+    assert not lanes(32, 2048) and not lanes(64, 4096)
+    assert not lanes(16, 4096, dec)
 
 
 def test_input_scales_fold_into_a_quadratic_surrogate_and_its_bound():

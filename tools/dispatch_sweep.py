@@ -1,4 +1,4 @@
-"""The automatic layout dispatch (DeviceChains.run(layout='auto'): chains._small_problem, _trees_in_step and the library's own
+"""The automatic layout dispatch (DeviceChains.run(layout='auto'): layout.choose, chains._trees_in_step and the library's own
 rules) against every forced layout, over workload families it was NOT tuned on one by one: dimension x chain count x tree size
 (target_accept) x tree heterogeneity (per-dimension scales with the metric adaptation off) x feature set (plain, decay term,
 constraint transform).  For every cell: leapfrog steps/s of group / split / wave / auto in post-adaptation launches, the kernel
