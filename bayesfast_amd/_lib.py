@@ -118,10 +118,16 @@ SYMBOLS = {
     'bfhip_logmeanexp_stats': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp]),
     'bfhip_acor_moments': (C.c_int, [_vp, C.c_int, C.c_long, C.c_int, C.c_long, _vp, _vp, _vp]),
     'bfhip_acor_lag_sums': (C.c_int, [_vp, C.c_int, C.c_long, C.c_int, C.c_long, _vp, _vp, _vp, C.c_long, C.c_int, _vp, _vp]),
+    'bfhip_diag_columns': (C.c_int, [_vp, C.c_int, C.c_long, C.c_long, C.c_long, _vp, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, _vp,
+                                     _vp]),
+    'bfhip_diag_extent': (C.c_int, [_vp, C.c_int, C.c_long, _vp, _vp, _vp]),
+    'bfhip_diag_sort': (C.c_int, [_vp, C.c_long, _vp, C.c_int, _vp, _vp]),
+    'bfhip_diag_rank': (C.c_int, [_vp, C.c_long, _vp, _vp, C.c_int, _vp]),
     'bfhip_logp_hess': (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     'bfhip_laplace_opt': (C.c_int, [_vp, C.POINTER(LaplaceOpts), C.c_int, _vp, _vp, _vp, _vp, _vp]),
 }
 ACOR_MAX_GROUPS = 256   # walker groups of bfhip_acor_lag_sums: its work buffer is min(n_w, 256) * n_lag * n_d doubles
+DIAG_BATCH = 16         # BFHIP_DIAG_BATCH: parameters per batch of the bfhip_diag_* passes (the width of their series buffers)
 
 _lib = None
 

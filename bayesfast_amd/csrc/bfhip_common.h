@@ -18,6 +18,14 @@ __device__ inline double bf_logaddexp(double x, double y) {
     return tmp;  // NaN
 }
 
+// float64 -> uint64 whose unsigned order is the numeric order, every NaN last and -0 == +0 (numpy's sort order)
+__device__ inline uint64_t bf_order_key(double v) {
+    if (v != v) return ~0ull;
+    if (v == 0.) v = 0.;
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
 #define BF_HIP_CHECK(expr)                                                                 \
     do {                                                                                   \
         hipError_t _e = (expr);                                                            \

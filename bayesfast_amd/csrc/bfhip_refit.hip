@@ -7,14 +7,6 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include "bfhip_common.h"
 
-// float64 -> uint64 whose unsigned order is the numeric order, every NaN last and -0 == +0 (numpy's sort order)
-__device__ inline uint64_t bf_order_key(double v) {
-    if (v != v) return ~0ull;
-    if (v == 0.) v = 0.;
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
 __global__ void bf_keys_iota_kernel(long n, const double *__restrict__ a, uint64_t *__restrict__ keys, int64_t *__restrict__ idx) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {

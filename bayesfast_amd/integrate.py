@@ -256,6 +256,19 @@ def reference_classes(bayesfast=None):
 
         __call__ = get
 
+        # ---- the convergence checks of the device result, read where the sampler left it (the reference's TraceTuple has none) ----
+        def integrated_time(self, *args, **kwargs):
+            return self._inner.integrated_time(*args, **kwargs)
+
+        def rhat(self, *args, **kwargs):
+            return self._inner.rhat(*args, **kwargs)
+
+        def ess(self, *args, **kwargs):
+            return self._inner.ess(*args, **kwargs)
+
+        def summary(self, *args, **kwargs):
+            return self._inner.summary(*args, **kwargs)
+
         # ---- per-chain traces of the reference's own classes, for _get_step_size / _get_metric / users ----
         @property
         def _sample_traces(self):

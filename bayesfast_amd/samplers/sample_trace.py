@@ -420,6 +420,46 @@ class TraceTuple:
             x = torch.as_tensor(x)
         return acor.integrated_time_sharded(x, self.n_chain, c, tol, quiet)
 
+    def _diag_input(self, since_iter, include_warmup, original_space, return_type):
+        """What ``get(..., flatten=False)`` selects, as a view of this rank's parts (n_chain, n_t, n_d), unmaterialised."""
+        from .. import parallel
+        if parallel.world()[1] > 1:
+            raise NotImplementedError('rhat, ess and summary rank every value among the draws of ALL chains, and this TraceTuple '
+                                      'holds one rank\'s: gather the chains and use the host port, '
+                                      'utils.diagnostics.summary(tt.gather().get(flatten=False)).')
+        if since_iter is None:
+            since_iter = 0 if include_warmup else self.n_warmup
+        since_iter = int(since_iter)
+        if since_iter >= self.i_iter - 1:
+            raise ValueError('since_iter is too large. Nothing to return.')
+        if return_type == 'samples':
+            return self._parts['samples_original' if original_space else 'samples'][:, since_iter:]
+        if return_type == 'logp':
+            if original_space:
+                return self._parts['logp_original'][:, since_iter:, None]
+            return self._parts['stats'][:, since_iter:, 0:1]
+        raise ValueError('invalid value for return_type.')
+
+    def rhat(self, since_iter=None, include_warmup=False, original_space=True, return_type='samples', method='rank'):
+        """R-hat (n_d,) of the chains (``bayesfast_amd.utils.rhat``) over what ``get(since_iter, include_warmup, original_space,
+        return_type, flatten=False)`` selects (``'logp'``: n_d = 1), without materialising it: device parts are read in place,
+        host parts take the host port.  Single process only: with more than one rank it raises ``NotImplementedError``."""
+        from ..utils import diagnostics
+        return diagnostics.rhat(self._diag_input(since_iter, include_warmup, original_space, return_type), method)
+
+    def ess(self, since_iter=None, include_warmup=False, original_space=True, return_type='samples', method='bulk',
+            prob=(0.05, 0.95)):
+        """Effective sample size (n_d,) of the chains (``bayesfast_amd.utils.ess``); selection and limits as ``rhat``."""
+        from ..utils import diagnostics
+        return diagnostics.ess(self._diag_input(since_iter, include_warmup, original_space, return_type), method, prob)
+
+    def summary(self, since_iter=None, include_warmup=False, original_space=True, return_type='samples', probs=(0.05, 0.5, 0.95),
+                prob=(0.05, 0.95)):
+        """The table of mean, sd, quantiles, mcse_mean, ess_bulk, ess_tail and rhat per parameter
+        (``bayesfast_amd.utils.summary``); selection and limits as ``rhat``."""
+        from ..utils import diagnostics
+        return diagnostics.summary(self._diag_input(since_iter, include_warmup, original_space, return_type), probs, prob)
+
     def __getitem__(self, key):
         return self.sample_traces[key]
 

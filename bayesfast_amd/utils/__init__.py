@@ -1,5 +1,6 @@
 from .acor import integrated_time, AutocorrError
 from .resample import SystematicResampler
+from .diagnostics import rhat, ess, summary
 from .laplace import Laplace, LaplaceResult, make_positive
 
-__all__ = ['SystematicResampler', 'integrated_time', 'AutocorrError', 'Laplace', 'LaplaceResult', 'make_positive']
+__all__ = ['SystematicResampler', 'integrated_time', 'AutocorrError', 'Laplace', 'LaplaceResult', 'make_positive', 'rhat', 'ess', 'summary']

@@ -37,7 +37,8 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_DIM 128         /* input_size limit of the device path */
 #define BFHIP_MAX_TREEDEPTH 12
 
-/* 104: bfhip_logp_hess and bfhip_laplace_opt, the analytic Hessian of the surrogate density and the device Newton maximiser.
+/* 105: bfhip_diag_columns, bfhip_diag_extent, bfhip_diag_sort and bfhip_diag_rank, the data passes of split-R-hat, ESS and the posterior summary.
+ * 104: bfhip_logp_hess and bfhip_laplace_opt, the analytic Hessian of the surrogate density and the device Newton maximiser.
  * 103: bfhip_acor_moments and bfhip_acor_lag_sums, the device integrated autocorrelation time.  102 (round 6): bfhip_polar_ns
  * takes 2 d^2 + n_iter + 10 doubles of work.  101 (round 6): BFHIP_TREE_MODE_WORK grew to 4162 and
  * work[0] of bfhip_tree_size_mode_share carries the laggard bit; 100 before. */
@@ -482,6 +483,39 @@ int bfhip_polar_ns(bfhip_ctx *ctx, int d, const double *a, double *x, int n_iter
 int bfhip_acor_moments(bfhip_ctx *ctx, int n_w, long n_t, int n_d, long ldw, const double *x, double *mean, double *inv);
 int bfhip_acor_lag_sums(bfhip_ctx *ctx, int n_w, long n_t, int n_d, long ldw, const double *x, const double *mean, const double *inv,
                         long t0, int n_lag, double *work, double *out);
+
+/* Convergence diagnostics of many chains (rank-normalised split-R-hat, bulk / tail / mean effective sample size and the table of
+ * mean, sd and quantiles: Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021; bayesfast_amd/utils/diagnostics.py holds the
+ * estimators and the walk over Geyer's sequence).  The data-sized passes, on a batch of at most BFHIP_DIAG_BATCH parameters:
+ *   bfhip_diag_columns  columns k0 .. k0 + nb - 1 of the time-major sample tensor -> out (2 n_chain, h, BFHIP_DIAG_BATCH), the
+ *                       split layout: chain c's rows since .. since + h - 1 are split chain 2 c, the next h rows split chain
+ *                       2 c + 1.  Element (c, row r, column k) is x[c ldw + r ldr + k] (ldr >= the row length, ldw free: a
+ *                       [:, since:] view goes in without a copy); x is float64, or float32 (is_f32) read as float64.
+ *                       mode BFHIP_DIAG_PLAIN: x; BFHIP_DIAG_FOLD: |x - c[b]|; BFHIP_DIAG_BELOW: 1 if x <= c[b], else 0 (c (nb,)
+ *                       device constants, one per column; not read in the plain mode).  Columns nb .. BFHIP_DIAG_BATCH - 1 of out
+ *                       are written as 0, so that every batch has one shape and the reductions over it one order.
+ *   bfhip_diag_extent   lo, hi (n_series, BFHIP_DIAG_BATCH) <- the smallest and the largest value of every split chain's column of a
+ *                       (n_series, h, BFHIP_DIAG_BATCH) series buffer (NaN draws are passed over; a column of NaN alone gives
+ *                       lo = inf, hi = -inf).  A parameter is constant exactly when the smallest lo equals the largest hi: an
+ *                       exact comparison, where the centred sum of squares of n copies of a constant depends on how their sum rounds.
+ *   bfhip_diag_sort     stable ascending sort of column b of a (n, BFHIP_DIAG_BATCH) series buffer: keys_sorted (n,) uint64 (the
+ *                       order-preserving keys of bfhip_sort_keys: every NaN last, -0 == +0), order (n,) uint32 the permutation.
+ *                       n <= 2^31 - 1.  The quantiles are read off keys_sorted.
+ *   bfhip_diag_rank     z[order[p] BFHIP_DIAG_BATCH + b] = ndtri((r_p - 3/8) / (n + 1/4)) for every sorted position p, r_p the
+ *                       1-based rank, tied values sharing the mean of their ranks (the tie run by lower / upper bound in
+ *                       keys_sorted).  z may be the buffer the column was sorted from.
+ * The chain moments and autocovariance sums of a series buffer are bfhip_acor_moments and bfhip_acor_lag_sums with n_w = 2 n_chain,
+ * n_t = h, n_d = BFHIP_DIAG_BATCH, ldw = h BFHIP_DIAG_BATCH and inv filled with 1.  Stream-ordered, no host synchronisation; every
+ * result is bitwise repeatable and does not depend on the batch or the column a parameter lands in. */
+#define BFHIP_DIAG_BATCH 16
+#define BFHIP_DIAG_PLAIN 0
+#define BFHIP_DIAG_FOLD 1
+#define BFHIP_DIAG_BELOW 2
+int bfhip_diag_columns(bfhip_ctx *ctx, int n_chain, long h, long ldw, long ldr, const void *x, int is_f32, long since, int k0, int nb,
+                       int mode, const double *c, double *out);
+int bfhip_diag_extent(bfhip_ctx *ctx, int n_series, long h, const double *series, double *lo, double *hi);
+int bfhip_diag_sort(bfhip_ctx *ctx, long n, const double *series, int b, uint64_t *keys_sorted, uint32_t *order);
+int bfhip_diag_rank(bfhip_ctx *ctx, long n, const uint64_t *keys_sorted, const uint32_t *order, int b, double *z);
 
 /* The OptimizeStep's Laplace approximation (utils/laplace.py:131-183; the reference differences the gradient with numdifftools, at
  * every Newton-CG iteration and once more at the maximum, one point per call).  Both calls take the uploaded SCALAR surrogate density
