@@ -42,15 +42,19 @@ __device__ inline double swap32_add_f64(double v) {
 }
 // Sums over the 64 lanes of N independent values, wave-uniform results in a fixed order.  The N reductions advance
 // step by step together so that the latency of each step is covered by the other values' instructions.
-// Default: two v_mfma_f64_4x4x4 per value (the matrix pipe is idle in the chain phase) and two row rotations; with
-// BF_WSUM_BUTTERFLY: four DPP butterfly steps inside the rows of 16 lanes and two gfx950 row swaps (11 % slower on the
-// headline workload, kept as the reference form of the reduction).
+// Default (wave_sum_n_packed): one v_mfma_f64_4x4x4 per value, then one more and two row rotations per FOUR values (the
+// FP64 vector instructions share the SIMD's pipe with the MFMAs, and the pipelined kernel's trip is bound by that pipe:
+// docs/EXPERIMENTS.md); with BF_WSUM_UNPACKED (wave_sum_n_unpacked): the second MFMA and the rotations once per value,
+// the same numbers; with BF_WSUM_BUTTERFLY: four DPP butterfly steps inside the rows of 16 lanes and two gfx950 row swaps
+// (11 % slower on the headline workload, kept as the reference form of the reduction).
+//
+// v_mfma_f64_4x4x4 is four 4 x 4 x 4 products, one per block b = (lane >> 2) & 3: A[i][k] comes from lane 16k + 4b + i,
+// B[k][j] from lane 16k + 4b + j, D[i][j] = sum_k A[i][k] B[k][j] (k ascending) lands in lane 16i + 4b + j.
+// With B = 1 the first MFMA leaves, in lane 16i + 4b + j, the sum of the four lanes 16k + 4b + i (k = 0..3); fed back as the
+// B operand with A = 1 the second sums those over i: every lane of block b holds the total of its block's 16 lanes; two row
+// rotations add the four blocks.
 template <int N>
-__device__ inline void wave_sum_n(double (&v)[N]) {
-#ifndef BF_WSUM_BUTTERFLY
-    // with B = 1 the first MFMA leaves, in lane 16i + 4b + j, the sum of the four lanes 16k + 4b + i (k = 0..3); fed
-    // back as the B operand with A = 1 the second sums those over i: every lane of block b = (lane >> 2) & 3 holds the
-    // total of its block's 16 lanes; two row rotations add the four blocks.
+__device__ inline void wave_sum_n_unpacked(double (&v)[N]) {
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] = __builtin_amdgcn_mfma_f64_4x4x4f64(v[i], 1., 0., 0, 0, 0);
 #pragma unroll
@@ -59,6 +63,50 @@ __device__ inline void wave_sum_n(double (&v)[N]) {
     for (int i = 0; i < N; ++i) v[i] += dpp_f64<0x128>(v[i]);  // row_ror:8
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] += dpp_f64<0x124>(v[i]);  // row_ror:4
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = rfl(v[i]);
+}
+// The first MFMA's result is the same in the four columns j of a block, and the second MFMA and the rotations (by 8 and 4
+// lanes) never mix columns: the unpacked form does the same arithmetic four times over.  Here column j carries value
+// 4 c + j of pack c -- the operand of the second step takes lane l from value (l & 3) -- and value 4 c + j is read from
+// lane j.  Every column sees the operations of the unpacked form in the same order: bit-identical results, and a NaN or
+// an infinity stays in its own value's column.  (Like the rotations of the unpacked form, this wants all 64 lanes active:
+// the callers reduce under wave-uniform control flow only.)
+template <int N>
+__device__ inline void wave_sum_n_packed(double (&v)[N]) {
+    if constexpr (N == 1) {
+        wave_sum_n_unpacked<1>(v);
+    } else {
+        constexpr int NP = (N + 3) / 4;
+        const bool odd = threadIdx.x & 1, upper = threadIdx.x & 2;   // bits 0 and 1 of the lane
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] = __builtin_amdgcn_mfma_f64_4x4x4f64(v[i], 1., 0., 0, 0, 0);
+        double pk[NP];
+#pragma unroll
+        for (int c = 0; c < NP; ++c) {
+            const int b = 4 * c, m = (N - b < 4) ? N - b : 4;   // the values of this pack; a column without one repeats another
+            const int i1 = m >= 2 ? b + 1 : b, i2 = m >= 3 ? b + 2 : b, i3 = m >= 4 ? b + 3 : i2;
+            // (selects between values, not between the array's elements: those would keep the array in scratch memory)
+            const double a0 = v[b], a1 = v[i1], a2 = v[i2], a3 = v[i3];
+            const double lo = odd ? a1 : a0, hi = odd ? a3 : a2;
+            pk[c] = (m >= 3) ? (upper ? hi : lo) : lo;
+        }
+#pragma unroll
+        for (int c = 0; c < NP; ++c) pk[c] = __builtin_amdgcn_mfma_f64_4x4x4f64(1., pk[c], 0., 0, 0, 0);
+#pragma unroll
+        for (int c = 0; c < NP; ++c) pk[c] += dpp_f64<0x128>(pk[c]);  // row_ror:8
+#pragma unroll
+        for (int c = 0; c < NP; ++c) pk[c] += dpp_f64<0x124>(pk[c]);  // row_ror:4
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] = (i & 3) ? readlane_f64(pk[i >> 2], i & 3) : rfl(pk[i >> 2]);
+    }
+}
+template <int N>
+__device__ inline void wave_sum_n(double (&v)[N]) {
+#if defined(BF_WSUM_UNPACKED)
+    wave_sum_n_unpacked<N>(v);
+#elif !defined(BF_WSUM_BUTTERFLY)
+    wave_sum_n_packed<N>(v);
 #else
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] += dpp_f64<0xB1>(v[i]);   // quad_perm [1,0,3,2]
@@ -72,9 +120,9 @@ __device__ inline void wave_sum_n(double (&v)[N]) {
     for (int i = 0; i < N; ++i) v[i] = swap16_add_f64(v[i]);
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] = swap32_add_f64(v[i]);
-#endif
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] = rfl(v[i]);
+#endif
 }
 __device__ inline double wave_sum(double v) {
     double t[1] = {v};

@@ -546,6 +546,18 @@ typedef struct {
 int bfhip_laplace_opt(bfhip_ctx *ctx, const bfhip_laplace_opts *opts, int n_start, const double *x0, double *x, double *logp,
                       double *hess, double *info);
 
+/* The sampler kernels' sum over the 64 lanes of a wave (csrc/bfhip_wave.h: v_mfma_f64_4x4x4 steps on the matrix pipe and two row
+ * rotations), on given lane values: in (n_batch, n_val, 64) -> out (n_batch, n_val), n_val values reduced together as the kernels
+ * reduce them, 1 <= n_val <= BFHIP_WSUM_MAX.  form BFHIP_WSUM_BUILT is the form the library's kernels were built with,
+ * BFHIP_WSUM_PACKED the second step shared by four values, BFHIP_WSUM_UNPACKED the second step once per value; all three give the
+ * same bits (tests/test_gpu_wave_sum.py holds them to that and to an emulation of the instruction's lane maps).  A check of the
+ * reduction on the device it runs on, not a compute path.  Stream-ordered, no host synchronisation. */
+#define BFHIP_WSUM_MAX 7
+#define BFHIP_WSUM_BUILT 0
+#define BFHIP_WSUM_PACKED 1
+#define BFHIP_WSUM_UNPACKED 2
+int bfhip_wave_sum_probe(bfhip_ctx *ctx, int n_batch, int n_val, int form, const double *in, double *out);
+
 /* NOT part of this interface: the library's test and tuning switches (force a chain layout, a kernel form or a chains-per-workgroup
  * count; attach measurement buffers; run a launch in one part).  They have ONE entry point each for integers and for buffers,
  * declared with their keys in include/bfhip_debug.h; they never change what a call computes, and a binding has no use for them. */

@@ -2,7 +2,9 @@
 bfhip_sampler.hip: tools/svariant.sh trace -DBF_TRACE=24 (the stamps live in LDS: 3 KB is what the decay instantiation leaves), selected with BFHIP_LIBRARY) on config 4's funnel (decay
 instantiation) or the plain Gaussian: phase A (0-1), barrier B1 (1-2), phase B = MFMA chain + pending bookkeeping (2-5), barrier
 B2 (5-6), phase C up to / through its first reduction (6-7-8), rest of phase C (8 - next trip's 0).
-usage:  BFHIP_LIBRARY=bayesfast_amd/variants/libbfhip_s_trace.so python tools/trace_pipe.py [funnel|plain] [chains]"""
+banana: the headline (bench.py's config 3, both rounds as the benchmark runs them); the stamps left at the end are those of the second
+round's timed launch, the one where every leaf is outside the bound.
+usage:  BFHIP_LIBRARY=bayesfast_amd/variants/libbfhip_s_trace.so python tools/trace_pipe.py [funnel|plain|banana] [chains]"""
 import sys, os, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -18,7 +20,13 @@ NT = 24
 ctx = get_context(0)
 d = 64
 rng = np.random.default_rng(2024)
-if what == 'funnel':
+if what == 'banana':
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from benchlib import blocks
+    buf = torch.zeros(NT * 16, dtype=torch.int64, device=ctx.device)
+    _lib.debug_buffer('stamps', buf)   # (every launch of a traced kernel writes it: the last one stays)
+    blocks.config3_rounds(ctx, 2024, Cn, 100, 200, 1, 1)
+elif what == 'funnel':
     logp = funnel_logp(d)
     su = bfa.PolyModel('quadratic', input_size=d, output_size=1)
     den = bfa.SurrogateDensity(su, decay_options=dict(use_decay=True))
@@ -32,12 +40,12 @@ else:
     dd = DeviceDensity(spec, ctx)
     x0 = rng.normal(size=(Cn, d))
     kw = dict(n_warmup=300, check=False, layout='wave')
-ch = DeviceChains(dd, x0, seed=5)
-ch.run(300, 'NUTS', **kw)
-buf = torch.zeros(NT * 16, dtype=torch.int64, device=ctx.device)
-L = _lib.lib()
-_lib.debug_buffer('stamps', buf)
-ch.run(4, 'NUTS', **kw)
+if what != 'banana':
+    ch = DeviceChains(dd, x0, seed=5)
+    ch.run(300, 'NUTS', **kw)
+    buf = torch.zeros(NT * 16, dtype=torch.int64, device=ctx.device)
+    _lib.debug_buffer('stamps', buf)
+    ch.run(4, 'NUTS', **kw)
 torch.cuda.synchronize()
 _lib.debug_buffer('stamps', None)
 print(_lib.last_kernel())
