@@ -125,8 +125,11 @@ SYMBOLS = {
     'bfhip_diag_rank': (C.c_int, [_vp, C.c_long, _vp, _vp, C.c_int, _vp]),
     'bfhip_logp_hess': (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     'bfhip_laplace_opt': (C.c_int, [_vp, C.POINTER(LaplaceOpts), C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    'bfhip_pipeline_logp_hess': (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    'bfhip_pipeline_laplace_opt': (C.c_int, [_vp, C.POINTER(LaplaceOpts), C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     'bfhip_wave_sum_probe': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
 }
+HESS_FULL, HESS_GAUSS_NEWTON = 0, 1   # BFHIP_HESS_FULL / _GAUSS_NEWTON: hess_kind of the bfhip_pipeline_* Hessian calls
 WSUM_MAX = 7            # BFHIP_WSUM_MAX: values bfhip_wave_sum_probe reduces together
 WSUM_FORMS = {'built': 0, 'packed': 1, 'unpacked': 2}   # BFHIP_WSUM_BUILT / _PACKED / _UNPACKED
 ACOR_MAX_GROUPS = 256   # walker groups of bfhip_acor_lag_sums: its work buffer is min(n_w, 256) * n_lag * n_d doubles

@@ -360,3 +360,10 @@ class Chi2PipelineDensity(SurrogateDensity):
 
     def grad(self, x, original_space=True):
         return self.logp_and_grad(x, original_space)[1]
+
+    def hess(self, x, original_space=True, gauss_newton=False):
+        """The analytic Hessian of ``logp`` at x (d,) or (n, d): (d, d) or (n, d, d), symmetric
+        (``DeviceDensity.pipeline_logp_grad_hess``).  ``gauss_newton=True``: without the terms that carry the residual, so that the
+        likelihood part is negative semi-definite.  NotImplementedError for a surrogate that the device streams in chunks."""
+        x = np.asarray(x, dtype=np.float64)
+        return self.device().pipeline_logp_grad_hess(x, original_space, gauss_newton)[2].cpu().numpy()

@@ -69,6 +69,8 @@ struct bfhip_ctx {
     int n_cu;
     void *flow;           // counters and exchange buffers of the triangular solves (bfhip_fit.hip: ensure_flow)
     size_t flow_bytes;
+    void *hess_work;      // per-workgroup slots of the pipeline density's Hessian (bfhip_pld_hess.h: G and G^T G; grow-only)
+    size_t hess_work_bytes;
 };
 
 // Every entry point that launches or allocates runs on its context's device, whatever the caller's current device is

@@ -398,17 +398,23 @@ __host__ __device__ inline void bf_newton_solve(BfNewtonWork &nw, int d, int tid
     BF_HESS_SYNC();
 }
 
-struct BfNewtonResult {
+// what the iteration itself returns; the evaluation (below) keeps the rest
+struct BfNewtonStat {
     double logp;
     int n_iter, status;
     double last_step, lam;
-    BfHessPt pt;   // the evaluation at the returned point: nw.x, with H in the upper triangle of M and hd, the gradient in gc
 };
 
-__host__ __device__ inline BfNewtonResult bf_newton_max(const DevModel &m, const double *x0, int max_iter, double xtol, BfHessWork &w,
-                                                        BfNewtonWork &nw, int tid, int nt) {
-    const int d = m.d;
-    BfNewtonResult res;
+// The iteration on any evaluation Ev of a team:
+//   double Ev::eval(const double *x, int tid, int nt)   logp at x, and whatever store needs, left in the evaluation's own work arrays;
+//                                                       all threads call it, its last barrier passed on return
+//   void Ev::store(BfNewtonWork &nw, int tid, int nt)   H of the LAST eval -> upper triangle of nw.M and nw.hd, its gradient -> nw.gc,
+//                                                       then a barrier
+// On return the last eval was taken at the returned point nw.x and stored.
+template <class Ev>
+__host__ __device__ inline BfNewtonStat bf_newton_run(Ev &ev, int d, const double *x0, int max_iter, double xtol, BfNewtonWork &nw, int tid,
+                                                      int nt) {
+    BfNewtonStat res;
     res.n_iter = 0;
     res.status = 1;
     res.last_step = 0.;
@@ -416,17 +422,15 @@ __host__ __device__ inline BfNewtonResult bf_newton_max(const DevModel &m, const
     BF_HESS_SYNC();
     for (int i = tid; i < d; i += nt) nw.x[i] = x0[i];
     BF_HESS_SYNC();
-    BfHessPt pt = bf_hess_eval(m, nw.x, 0, w, tid, nt, 1);
-    bf_newton_store(m, w, pt, nw, tid, nt);
-    double f = pt.logp, lam_prev = 0.;
+    double f = ev.eval(nw.x, tid, nt), lam_prev = 0.;
+    ev.store(nw, tid, nt);
     if (!bf_finite(f)) res.status = 2;
     for (int it = 0; it < max_iter && res.status == 1; ++it) {
         double hmax = 0.;
         for (int i = 0; i < d; ++i) hmax = fmax(hmax, fabs(nw.hd[i]));
         const double lam0 = hmax > 0. ? 1e-3 * hmax : 1e-3;
-        double lam = 0., ms = 0.;
+        double lam = 0., ms = 0., ft = f;
         int accepted = 0;
-        BfHessPt ptt = pt;
         for (int n_try = 0; n_try < BF_NEWTON_MAX_RAISE; ++n_try) {
             if (bf_newton_chol(nw, d, lam, tid, nt)) {
                 bf_newton_solve(nw, d, tid, nt);
@@ -445,9 +449,9 @@ __host__ __device__ inline BfNewtonResult bf_newton_max(const DevModel &m, const
                 }
                 for (int i = tid; i < d; i += nt) nw.xt[i] = nw.x[i] + nw.r[i];
                 BF_HESS_SYNC();
-                ptt = bf_hess_eval(m, nw.xt, 0, w, tid, nt, 1);
+                ft = ev.eval(nw.xt, tid, nt);
                 // (near the maximum the increase falls below the rounding of logp itself)
-                if (bf_finite(ptt.logp) && ptt.logp >= f - 1e-13 * fmax(1., fabs(f))) {
+                if (bf_finite(ft) && ft >= f - 1e-13 * fmax(1., fabs(f))) {
                     accepted = 1;
                     break;
                 }
@@ -459,14 +463,13 @@ __host__ __device__ inline BfNewtonResult bf_newton_max(const DevModel &m, const
             if (res.status == 1) res.status = 3;   // (BF_NEWTON_MAX_RAISE)
             if (res.status == 3 && !(res.lam > 0.)) res.lam = lam;
             // the work vectors may hold a rejected trial point: evaluate the point that is returned
-            pt = bf_hess_eval(m, nw.x, 0, w, tid, nt, 1);
-            bf_newton_store(m, w, pt, nw, tid, nt);
+            (void)ev.eval(nw.x, tid, nt);   // (f is logp at nw.x already)
+            ev.store(nw, tid, nt);
             break;
         }
         for (int i = tid; i < d; i += nt) nw.x[i] = nw.xt[i];
-        pt = ptt;
-        f = pt.logp;
-        bf_newton_store(m, w, pt, nw, tid, nt);   // (its barrier also publishes x)
+        f = ft;
+        ev.store(nw, tid, nt);   // (its barrier also publishes x)
         res.n_iter = it + 1;
         res.last_step = ms;
         res.lam = lam;
@@ -474,6 +477,38 @@ __host__ __device__ inline BfNewtonResult bf_newton_max(const DevModel &m, const
         if (lam == 0. && ms <= xtol) res.status = 0;
     }
     res.logp = f;
-    res.pt = pt;
+    return res;
+}
+
+// ---- the scalar surrogate density as that evaluation ----
+struct BfScalarNewtonEval {
+    const DevModel &m;
+    BfHessWork &w;
+    BfHessPt pt;
+    __host__ __device__ double eval(const double *x, int tid, int nt) {
+        pt = bf_hess_eval(m, x, 0, w, tid, nt, 1);
+        return pt.logp;
+    }
+    __host__ __device__ void store(BfNewtonWork &nw, int tid, int nt) { bf_newton_store(m, w, pt, nw, tid, nt); }
+};
+
+struct BfNewtonResult {
+    double logp;
+    int n_iter, status;
+    double last_step, lam;
+    BfHessPt pt;   // the evaluation at the returned point: nw.x, with H in the upper triangle of M and hd, the gradient in gc
+};
+
+__host__ __device__ inline BfNewtonResult bf_newton_max(const DevModel &m, const double *x0, int max_iter, double xtol, BfHessWork &w,
+                                                        BfNewtonWork &nw, int tid, int nt) {
+    BfScalarNewtonEval ev = {m, w, BfHessPt()};
+    const BfNewtonStat st = bf_newton_run(ev, m.d, x0, max_iter, xtol, nw, tid, nt);
+    BfNewtonResult res;
+    res.logp = st.logp;
+    res.n_iter = st.n_iter;
+    res.status = st.status;
+    res.last_step = st.last_step;
+    res.lam = st.lam;
+    res.pt = ev.pt;
     return res;
 }

@@ -69,8 +69,9 @@ __global__ __launch_bounds__(LP_TH) void bf_laplace_opt_kernel(DevModel m, int n
 static int lp_check(bfhip_ctx *ctx, const char *who) {
     if (!ctx->has_model) return bf_set_error(BFHIP_ERR_STATE, "%s: no density uploaded", who);
     if (ctx->model.pld.on)
-        return bf_set_error(BFHIP_ERR_UNSUPPORTED, "%s: the analytic Hessian covers the scalar surrogate density, not the pipeline density "
-                                                   "(multi-output surrogate + Gaussian likelihood); difference bfhip_logp_grad instead", who);
+        return bf_set_error(BFHIP_ERR_UNSUPPORTED, "%s: this call covers the scalar surrogate density, not the pipeline density "
+                                                   "(multi-output surrogate + Gaussian likelihood): use bfhip_pipeline_logp_hess / "
+                                                   "bfhip_pipeline_laplace_opt", who);
     return 0;
 }
 

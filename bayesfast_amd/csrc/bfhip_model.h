@@ -51,6 +51,11 @@ struct PldDev {
     const double *yw, *fmuw;    // (MP) whitened data vector and f_mu, zero padded
     const unsigned *mono;       // (PP) i1 | i2 << 8 | i3 << 16; index DP = 1, DP + 1 = 0 (padding monomials)
     const unsigned long long *gtab;   // [n_ent][DP]: low word = monomial p, high word = a | b << 8 | mult << 16 (padding: a = DP + 1)
+    // second derivatives of the monomials, CSR over the ordered pairs (i <= j), pair number i (2 d - i + 1) / 2 + (j - i): the monomials
+    // that hold both coordinates, in increasing p.  Entry: low word = p, high word = rest | mult << 8 with d2 phi_p / dx_i dx_j =
+    // mult x_rest (rest = DP: the constant one).  Resident form only (NULL in the streamed form).
+    const int *h2ptr;                   // [d (d + 1) / 2 + 1]
+    const unsigned long long *h2ent;    // [h2ptr[last]]
     const double *prior_mu, *prior_prec;   // (DP) original-space Gaussian prior, zero padded (prec 0 = no prior on that input)
     double logp0, prior_c0;
     // streamed form (bfhip_pld.h: pld_eval_stream_q8), taken where the resident LDS block does not fit (or pld_stream = 1); then

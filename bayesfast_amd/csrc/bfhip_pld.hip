@@ -223,6 +223,43 @@ extern "C" int bfhip_pipeline_upload(bfhip_ctx *ctx, const bfhip_pipeline_desc *
     for (int j = 0; j < DP; ++j)
         for (size_t i = 0; i < per_dim[j].size(); ++i) gtab[i * DP + j] = per_dim[j][i];
 
+    // ---- second derivatives per ordered pair of inputs (bfhip_pld_hess.h): d2 phi_p / dx_i dx_j = mult x_rest ----
+    std::vector<int> h2ptr((size_t)d * (d + 1) / 2 + 1, 0);
+    std::vector<unsigned long long> h2ent;
+    {
+        std::vector<std::vector<unsigned long long>> per_pair((size_t)d * (d + 1) / 2);
+        for (int p = 0; p < nf; ++p) {   // (p outermost: every pair's entries in increasing p)
+            const int *ix = mono[p].i;
+            int vars[3], ex[3], nv = 0;
+            for (int q = 0; q < 3; ++q) {
+                if (ix[q] >= d) continue;
+                int at = -1;
+                for (int k = 0; k < nv; ++k) at = vars[k] == ix[q] ? k : at;
+                if (at < 0) { vars[nv] = ix[q]; ex[nv++] = 1; }
+                else ++ex[at];
+            }
+            for (int a = 0; a < nv; ++a)
+                for (int b = a; b < nv; ++b) {
+                    const int mult = a == b ? ex[a] * (ex[a] - 1) : ex[a] * ex[b];
+                    if (!mult) continue;
+                    const int i = vars[a] < vars[b] ? vars[a] : vars[b], j = vars[a] < vars[b] ? vars[b] : vars[a];
+                    int rest = ONE;   // what is left of the monomial without one x_i and one x_j
+                    bool di = false, dj = false;
+                    for (int q = 0; q < 3; ++q) {
+                        if (!di && ix[q] == i) { di = true; continue; }
+                        if (!dj && ix[q] == j) { dj = true; continue; }
+                        rest = ix[q];
+                    }
+                    const unsigned hi = (unsigned)rest | ((unsigned)mult << 8);
+                    per_pair[(size_t)i * (2 * d - i + 1) / 2 + (j - i)].push_back((unsigned long long)(unsigned)p | ((unsigned long long)hi << 32));
+                }
+        }
+        for (size_t q = 0; q < per_pair.size(); ++q) {
+            h2ent.insert(h2ent.end(), per_pair[q].begin(), per_pair[q].end());
+            h2ptr[q + 1] = (int)h2ent.size();
+        }
+    }
+
     // ---- K-split of GEMM2: the fewest rounds x steps per job that fits the CU's LDS with the sampler's own regions ----
     dm.pld.on = 1;   // (the LDS size below depends on it)
     const size_t base_bytes = bf_sampler_lds_bytes_base(dm);
@@ -312,7 +349,7 @@ extern "C" int bfhip_pipeline_upload(bfhip_ctx *ctx, const bfhip_pipeline_desc *
             if (!(ds->prior_prec[i] >= 0.)) return bf_set_error(BFHIP_ERR_ARG, "bfhip_pipeline_upload: prior_prec should be non-negative");
         }
     const size_t n_dbl = CF.size() + CTF.size() + 2 * (size_t)MP + prior.size();
-    const size_t bytes = n_dbl * 8 + gtab.size() * 8 + mono_tab.size() * 4 + 64;
+    const size_t bytes = n_dbl * 8 + gtab.size() * 8 + h2ent.size() * 8 + mono_tab.size() * 4 + h2ptr.size() * 4 + 64;
     if (int rc = bf_grow(ctx, &ctx->pld_buf, &ctx->pld_bytes, bytes)) return rc;
     std::vector<char> hb(bytes, 0);
     double *hd = (double *)hb.data();
@@ -323,7 +360,10 @@ extern "C" int bfhip_pipeline_upload(bfhip_ctx *ctx, const bfhip_pipeline_desc *
     const size_t o_f = o; memcpy(hd + o, fmuw.data(), (size_t)MP * 8); o += MP;
     const size_t o_pr = o; memcpy(hd + o, prior.data(), prior.size() * 8); o += prior.size();
     const size_t o_g = o; memcpy(hd + o, gtab.data(), gtab.size() * 8); o += gtab.size();
+    const size_t o_h2 = o; if (!h2ent.empty()) memcpy(hd + o, h2ent.data(), h2ent.size() * 8); o += h2ent.size();
     const size_t o_m = o; memcpy(hd + o, mono_tab.data(), mono_tab.size() * 4);
+    const size_t o_hp = o_m * 8 + mono_tab.size() * 4;   // (bytes: the pair pointers follow the monomial words)
+    memcpy(hb.data() + o_hp, h2ptr.data(), h2ptr.size() * 4);
     BF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     BF_HIP_CHECK(hipMemcpy(ctx->pld_buf, hb.data(), bytes, hipMemcpyHostToDevice));
     const double *dbase = (const double *)ctx->pld_buf;
@@ -346,6 +386,8 @@ extern "C" int bfhip_pipeline_upload(bfhip_ctx *ctx, const bfhip_pipeline_desc *
     pl.CS = stream ? dbase + o_cf : NULL;
     pl.gtabc = stream ? (const unsigned long long *)(dbase + o_g) : NULL;
     pl.mono = (const unsigned *)(dbase + o_m);
+    pl.h2ent = stream ? NULL : (const unsigned long long *)(dbase + o_h2);
+    pl.h2ptr = stream ? NULL : (const int *)((const char *)ctx->pld_buf + o_hp);
     pl.logp0 = ds->logp0 - 0.5 * k_yy;   // (the part of the data vector outside the surrogate's column space: a constant)
     pl.prior_c0 = ds->prior_c0;
     ctx->has_model = 1;

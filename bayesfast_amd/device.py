@@ -371,7 +371,7 @@ class DeviceDensity:
     def logp_grad_hess(self, x, original_space=False):
         """x: (n, d) or (d,) -> (logp (n,), grad (n, d), hess (n, d, d)) float64 device tensors: the analytic Hessian of the
         function ``logp_and_grad`` returns (``bfhip_logp_hess``), symmetric bit for bit.  A pipeline density (a spec with a
-        ``'chi2'`` stage) raises NotImplementedError: difference its gradient instead (``utils.laplace``)."""
+        ``'chi2'`` stage) raises NotImplementedError: it has ``pipeline_logp_grad_hess``."""
         torch = _torch()
         self.upload_if_needed()
         xt = self.ctx.tensor(x, torch.float64)
@@ -401,6 +401,44 @@ class DeviceDensity:
         opts = _lib.LaplaceOpts(int(max_iter), float(xtol))
         _lib.check(self.ctx._lib.bfhip_laplace_opt(self.ctx.handle, C.byref(opts), n, _ptr(xt), _ptr(out['x']), _ptr(out['logp']),
                                                    _ptr(out['hess']), _ptr(out['info'])))
+        return out
+
+    def pipeline_logp_grad_hess(self, x, original_space=False, gauss_newton=False):
+        """``logp_grad_hess`` for a pipeline density (a spec with a ``'chi2'`` stage; ``bfhip_pipeline_logp_hess``): x (n, d) or (d,) ->
+        (logp (n,), grad (n, d), hess (n, d, d)), the analytic Hessian of the function ``logp_and_grad`` returns, symmetric bit for
+        bit.  ``gauss_newton=True`` drops every term that carries the residual: the likelihood part is then negative semi-definite by
+        construction.  The first call, and any call with more points (up to two per CU) than every call before it, grows the context's
+        work buffer, which synchronises the stream and allocates: make one such call before capturing a graph or timing.
+        NotImplementedError for a scalar density, for the streamed form of the pipeline density and where one
+        workgroup's LDS or work buffer would pass the limit."""
+        torch = _torch()
+        self.upload_if_needed()
+        xt = self.ctx.tensor(x, torch.float64)
+        single = xt.dim() == 1
+        xt = xt.reshape(-1, self.d)
+        n = xt.shape[0]
+        logp = self.ctx.empty((n,))
+        grad = self.ctx.empty((n, self.d))
+        hess = self.ctx.empty((n, self.d, self.d))
+        kind = _lib.HESS_GAUSS_NEWTON if gauss_newton else _lib.HESS_FULL
+        _lib.check(self.ctx._lib.bfhip_pipeline_logp_hess(self.ctx.handle, n, _ptr(xt), int(bool(original_space)), kind, _ptr(logp),
+                                                          _ptr(grad), _ptr(hess)))
+        return (logp[0], grad[0], hess[0]) if single else (logp, grad, hess)
+
+    def pipeline_maximize(self, x0, max_iter=200, xtol=1e-5, gauss_newton=False):
+        """``maximize`` for a pipeline density (``bfhip_pipeline_laplace_opt``): the same iteration, the same dict of results.
+        ``gauss_newton`` selects both the matrix the iteration steps on and the one returned as ``hess``.  NotImplementedError as
+        ``pipeline_logp_grad_hess``."""
+        torch = _torch()
+        self.upload_if_needed()
+        xt = self.ctx.tensor(x0, torch.float64).reshape(-1, self.d)
+        n = xt.shape[0]
+        out = dict(x=self.ctx.empty((n, self.d)), logp=self.ctx.empty((n,)), hess=self.ctx.empty((n, self.d, self.d)),
+                   info=self.ctx.empty((n, 4)))
+        opts = _lib.LaplaceOpts(int(max_iter), float(xtol))
+        kind = _lib.HESS_GAUSS_NEWTON if gauss_newton else _lib.HESS_FULL
+        _lib.check(self.ctx._lib.bfhip_pipeline_laplace_opt(self.ctx.handle, C.byref(opts), kind, n, _ptr(xt), _ptr(out['x']),
+                                                            _ptr(out['logp']), _ptr(out['hess']), _ptr(out['info'])))
         return out
 
     _WHICH = {'from_original': 0, 'from_original_grad': 1, 'from_original_grad2': 2, 'to_original': 3,

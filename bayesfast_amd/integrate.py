@@ -620,9 +620,7 @@ def patch(bayesfast=None, fallback=False, laplace=False):
                 flag = self.density.use_surrogate
                 self.density.use_surrogate = True
                 try:
-                    den = as_surrogate_density(self.density)
-                    if den.spec().get('chi2') is not None:   # (the pipeline density: the host route, through the recipe's lambdas)
-                        den = None
+                    den = as_surrogate_density(self.density)   # (a SurrogateDensity, or a Chi2PipelineDensity for model-chi2-prior)
                 except NotImplementedError:
                     den = None
                 finally:

@@ -2,12 +2,15 @@
 
 Two routes behind one ``Laplace.run``:
 
-* **device** -- ``logp`` is a ``SurrogateDensity`` (or its bound ``logp``), the method is the default ``'Newton-CG'`` and no
-  ``grad`` / ``hess`` callables are given: every start is maximised inside ONE launch by a damped Newton iteration on the
-  analytic Hessian (``DeviceDensity.maximize``, ``bfhip_laplace_opt``), and the covariance comes from that Hessian -- exact, where
+* **device** -- ``logp`` is a ``SurrogateDensity`` or a ``Chi2PipelineDensity`` (or its bound ``logp``), the method is the default
+  ``'Newton-CG'`` and no ``grad`` / ``hess`` callables are given: every start is maximised inside ONE launch by a damped Newton
+  iteration on the analytic Hessian (``DeviceDensity.maximize``, ``bfhip_laplace_opt``; for the pipeline density
+  ``DeviceDensity.pipeline_maximize``, ``bfhip_pipeline_laplace_opt``), and the covariance comes from that Hessian -- exact, where
   the reference differences the gradient with ``numdifftools`` at every iteration.  Works in the sampling space
-  (``original_space=False``), as the recipe does.
-* **host** -- everything else (a ``Chi2PipelineDensity``, another ``optimize_method``, user callables):
+  (``original_space=False``), as the recipe does.  For the pipeline density ``hess_options={'gauss_newton': True}`` steps on, and
+  returns, the Gauss-Newton matrix (no term that carries the residual: its likelihood part is negative semi-definite).  A pipeline
+  density the device refuses (a surrogate it streams in chunks) takes the host route, silently.
+* **host** -- everything else (another ``optimize_method``, user callables):
   ``scipy.optimize.minimize`` as the reference runs it.  Where ``logp`` is one of this package's densities the gradient is the
   device's and a missing Hessian is ONE launch of the gradient on the 4 d points of a fourth-order central difference; plain
   callables are differenced the same way.  Nothing imports ``numdifftools``.
@@ -162,7 +165,8 @@ def _negated(fn):
 class Laplace:
     """Evaluating and sampling the Laplace approximation of a target density, with the arguments, defaults and messages of
     ``bayesfast.utils.Laplace``.  ``grad_options`` / ``hess_options`` went to ``numdifftools`` there; here their ``'step'`` entry
-    sets the difference step of the host route and the rest is accepted and unused."""
+    sets the difference step of the host route, ``hess_options['gauss_newton']`` selects the Gauss-Newton matrix on the device route of
+    a pipeline density, and the rest is accepted and unused."""
 
     def __init__(self, optimize_method='Newton-CG', optimize_tol=1e-5, optimize_options=None, max_cond=1e5, n_sample=2000, beta=1.,
                  mvn_generator=None, grad_options=None, hess_options=None):
@@ -179,15 +183,19 @@ class Laplace:
         den = _our_density(logp)
         if den is None and not callable(logp):
             raise ValueError('logp should be callable.')
-        device_route = (den is not None and self._optimize_method == 'Newton-CG' and not callable(grad) and not callable(hess)
-                        and den.spec().get('chi2') is None)
+        device_route = den is not None and self._optimize_method == 'Newton-CG' and not callable(grad) and not callable(hess)
         try:
             x_0 = np.atleast_1d(np.asarray(x_0, dtype=np.float64))
         except (TypeError, ValueError):
             raise ValueError('invalid value for x_0.')
         if x_0.ndim != 1 and not (device_route and x_0.ndim == 2):
             raise ValueError('invalid value for x_0.')
-        opt, H = self._run_device(den, x_0) if device_route else self._run_host(den, logp, x_0, grad, hess)
+        run = self._run_device(den, x_0) if device_route else None
+        if run is None:   # (also: a pipeline density in a form the device's maximiser does not cover)
+            if x_0.ndim != 1:
+                raise ValueError('invalid value for x_0.')
+            run = self._run_host(den, logp, x_0, grad, hess)
+        opt, H = run
         if not opt.success:
             warnings.warn('the optimization stopped at {}, but maybe it has not converged yet.'.format(opt.x), RuntimeWarning)
         return self._result(opt, H, self._n_sample or min(1000, 10 * x_0.shape[-1]))
@@ -200,17 +208,29 @@ class Laplace:
                              beta=self._beta, opt_result=opt)
 
     def _run_device(self, den, x_0):
+        """(opt_result, H) of the device's maximiser; None where it refuses a pipeline density (the streamed form, an LDS need above
+        the limit): only that call's NotImplementedError is taken as a refusal, every other error is the caller's to see."""
         from scipy.optimize import OptimizeResult
         dev = den.device()
         xtol = 1e-5 if self._optimize_tol is None else self._optimize_tol
-        out = dev.maximize(np.atleast_2d(x_0), max_iter=int(self._optimize_options.get('maxiter', DEFAULT_MAX_ITER)), xtol=xtol)
+        max_iter = int(self._optimize_options.get('maxiter', DEFAULT_MAX_ITER))
+        if den.spec().get('chi2') is not None:   # the pipeline density: entry points of its own, and the choice of the matrix
+            gn = bool(self._hess_options.get('gauss_newton', False))
+            try:
+                out = dev.pipeline_maximize(np.atleast_2d(x_0), max_iter=max_iter, xtol=xtol, gauss_newton=gn)
+            except NotImplementedError:
+                return None
+            grad_at = lambda x: dev.logp_and_grad(x, False)[1].reshape(-1)   # (the gradient kernel: no Hessian is needed for it)
+        else:
+            out = dev.maximize(np.atleast_2d(x_0), max_iter=max_iter, xtol=xtol)
+            grad_at = lambda x: dev.logp_grad_hess(x, False)[1]
         fun, info = out['logp'].cpu().numpy(), out['info'].cpu().numpy()
         status = info[:, 1].astype(int)
         finite = np.where(np.isfinite(fun), fun, -np.inf)
         best = int(np.argmax(finite))   # (the first of equal maxima)
         x_best = out['x'][best].cpu().numpy()
         H = out['hess'][best].cpu().numpy()
-        _, g, _ = dev.logp_grad_hess(x_best, False)   # the gradient at the maximum, for opt_result.jac: one launch of one point
+        g = grad_at(x_best)   # the gradient at the maximum, for opt_result.jac: one launch of one point
         opt = OptimizeResult(x=x_best, fun=-float(fun[best]), jac=-g.cpu().numpy(), nit=int(info[best, 0]), nhev=int(info[best, 0]) + 1,
                              success=bool(status[best] == 0), status=int(status[best]), message=dev.MAXIMIZE_STATUS[status[best]],
                              all_x=out['x'].cpu().numpy(), all_fun=fun, all_status=status, last_step=float(info[best, 2]),

@@ -37,7 +37,9 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_DIM 128         /* input_size limit of the device path */
 #define BFHIP_MAX_TREEDEPTH 12
 
-/* 105: bfhip_diag_columns, bfhip_diag_extent, bfhip_diag_sort and bfhip_diag_rank, the data passes of split-R-hat, ESS and the posterior summary.
+/* 107: bfhip_pipeline_logp_hess and bfhip_pipeline_laplace_opt, the analytic and the Gauss-Newton Hessian of the pipeline density and
+ * its device Newton maximiser.  106: bfhip_wave_sum_probe.
+ * 105: bfhip_diag_columns, bfhip_diag_extent, bfhip_diag_sort and bfhip_diag_rank, the data passes of split-R-hat, ESS and the posterior summary.
  * 104: bfhip_logp_hess and bfhip_laplace_opt, the analytic Hessian of the surrogate density and the device Newton maximiser.
  * 103: bfhip_acor_moments and bfhip_acor_lag_sums, the device integrated autocorrelation time.  102 (round 6): bfhip_polar_ns
  * takes 2 d^2 + n_iter + 10 doubles of work.  101 (round 6): BFHIP_TREE_MODE_WORK grew to 4162 and
@@ -519,7 +521,8 @@ int bfhip_diag_rank(bfhip_ctx *ctx, long n, const uint64_t *keys_sorted, const u
 
 /* The OptimizeStep's Laplace approximation (utils/laplace.py:131-183; the reference differences the gradient with numdifftools, at
  * every Newton-CG iteration and once more at the maximum, one point per call).  Both calls take the uploaded SCALAR surrogate density
- * with every feature of bfhip_density_desc; a pipeline density (bfhip_pipeline_upload) is refused with BFHIP_ERR_UNSUPPORTED.
+ * with every feature of bfhip_density_desc; a pipeline density (bfhip_pipeline_upload) is refused with BFHIP_ERR_UNSUPPORTED
+ * and has bfhip_pipeline_logp_hess / bfhip_pipeline_laplace_opt below.
  *
  * bfhip_logp_hess: Density.logp / grad and the Hessian of logp for n points: x (n,d) -> logp (n,), grad (n,d) (either may be NULL),
  * hess (n,d,d) row-major.  The Hessian is the closed form of the function bfhip_logp_grad returns -- polynomial, surrogate input
@@ -545,6 +548,34 @@ typedef struct {
  * Stream-ordered, no host synchronisation. */
 int bfhip_laplace_opt(bfhip_ctx *ctx, const bfhip_laplace_opts *opts, int n_start, const double *x0, double *x, double *logp,
                       double *hess, double *info);
+
+/* The same two calls for the PIPELINE density (bfhip_pipeline_upload: multi-output surrogate, Gaussian likelihood, optional prior), in
+ * its resident forms (the sixteen- and eight-chain layouts), d <= BFHIP_MAX_DIM, with or without bound, decay term, transform, input
+ * scales and prior.  The Hessian is the closed form of the function bfhip_logp_grad returns for that density
+ * (csrc/bfhip_pld_hess.h has the derivation), symmetric bit for bit; on the surfaces beta = alpha and beta_d^2 = alpha_2 it takes the
+ * gradient's branch.  hess_kind selects the matrix:
+ *   BFHIP_HESS_FULL           H = -G^T G - sum_o r_o d2 f_o + (chain, prior, decay, transform terms), G the Jacobian of the (whitened,
+ *                             extrapolated) outputs in the scaled coordinates and r their residual
+ *   BFHIP_HESS_GAUSS_NEWTON   every term that carries the residual dropped: -a G^T G a, the prior's -prec_i J_i^2, the decay term and
+ *                             the transform's log-Jacobian term.  Its likelihood part is negative semi-definite by construction: what
+ *                             a Laplace covariance and a damped Newton step want far from the maximum.
+ * bfhip_pipeline_logp_hess: x (n,d) -> logp (n,), grad (n,d) (either may be NULL), hess (n,d,d) row-major.  A workgroup per point;
+ * the two dense contractions run on the FP64 matrix cores.
+ * bfhip_pipeline_laplace_opt: as bfhip_laplace_opt, same iteration, same statuses, info laid out the same; hess_kind selects both
+ * the matrix of the iteration and the one returned (hess may be NULL).
+ * BFHIP_ERR_UNSUPPORTED: a scalar density (use the two calls above); the streamed form of the pipeline density; an LDS or work-buffer
+ * need of one workgroup above the limit (the message names the numbers).  
+ * Work buffer: both calls need min(n, 2 per CU) slots of (MP + DG) DG doubles in a buffer that belongs to the context, only grows, is
+ * capped at 256 MB and is freed by bfhip_ctx_destroy.  A call that finds it too small SYNCHRONISES the stream and allocates: that call
+ * is neither stream-ordered nor fit for graph capture.  Warm the buffer up first -- one call with the largest n that will be used,
+ * for the density that will be used -- before capturing a graph or timing; every later call of at most that need is stream-ordered
+ * with no host synchronisation. */
+#define BFHIP_HESS_FULL 0
+#define BFHIP_HESS_GAUSS_NEWTON 1
+int bfhip_pipeline_logp_hess(bfhip_ctx *ctx, int n, const double *x, int original_space, int hess_kind, double *logp, double *grad,
+                             double *hess);
+int bfhip_pipeline_laplace_opt(bfhip_ctx *ctx, const bfhip_laplace_opts *opts, int hess_kind, int n_start, const double *x0, double *x,
+                               double *logp, double *hess, double *info);
 
 /* The sampler kernels' sum over the 64 lanes of a wave (csrc/bfhip_wave.h: v_mfma_f64_4x4x4 steps on the matrix pipe and two row
  * rotations), on given lane values: in (n_batch, n_val, 64) -> out (n_batch, n_val), n_val values reduced together as the kernels
