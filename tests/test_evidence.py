@@ -460,11 +460,13 @@ def test_device_spline_build_is_the_host_construction(kind):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('d', [5, 16, 48, 100, 128, 200, 256, 300])
+@pytest.mark.parametrize('d', [5, 16, 48, 100, 128, 200, 256, 300, 513, 640, 1024])
 def test_polar_ns_is_the_orthogonal_polar_factor(d):
     """bfhip_polar_ns (FastICA's symmetric decorrelation, scikit-learn's _sym_decorrelation as SIT calls it, transforms/sit.py:235-244)
     against the SVD's polar factor; its forms (X in LDS, a workgroup per row block, one grid barrier per step / the same with operands from L2 / a tile per
-    wave with two barriers) take bit-identical steps; residual reported, early stop, n_iter = 0."""
+    wave with two barriers) take bit-identical steps; residual reported, early stop, n_iter = 0.  Above d = 512 the multi-launch form
+    (one launch per product): d = 513 has 33 tiles a side, the last one a single row and column wide, and 129 k-steps (one ragged
+    step in a batch of eight); d = 640 fills every tile and batch; d = 1024 is the largest size taken."""
     import torch
     from bayesfast_amd import _lib
     from bayesfast_amd._lib import debug_set
@@ -499,6 +501,21 @@ def test_polar_ns_is_the_orthogonal_polar_factor(d):
     scale = np.sqrt(np.abs(A).sum(0).max() * np.abs(A).sum(1).max())
     np.testing.assert_allclose(x0, A / scale, rtol=1e-15)
     debug_set('polar_tiles', 0)
+
+
+@pytest.mark.gpu
+def test_polar_ns_refuses_more_than_1024_dimensions():
+    """d = 1025 is above what the multi-launch form's one-workgroup scale and residual kernels were written for: refused on the host,
+    naming the function, with nothing launched."""
+    import torch
+    from bayesfast_amd import _lib
+    from bayesfast_amd.device import get_context, _ptr
+    ctx = get_context(0)
+    buf = torch.full((64,), 7., dtype=torch.float64, device=ctx.device)
+    with pytest.raises(ValueError, match='bfhip_polar_ns'):
+        _lib.check(ctx._lib.bfhip_polar_ns(ctx.handle, 1025, _ptr(buf), _ptr(buf), 3, _ptr(buf), _ptr(buf[-1:])))
+    torch.cuda.synchronize(ctx.device)
+    assert buf.cpu().numpy().tolist() == [7.] * 64
 
 
 @pytest.mark.gpu

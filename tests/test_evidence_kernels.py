@@ -744,6 +744,15 @@ def test_data_kernels_refuse_bad_arguments_and_skip_empty_calls():
         'bfhip_sort_keys': [(-1, A, K, K), (4, N, K, K), (4, A, N, K), (4, A, K, N)],
         'bfhip_order_keys': [(-1, A, K), (4, N, K), (4, A, N)],
         'bfhip_count_keys': [(-1, K, 4, K, 0, K), (4, K, -1, K, 0, K), (4, N, 4, K, 0, K), (4, K, 4, N, 0, K), (4, K, 4, K, 1, N)],
+        # the FastICA iteration: (n, n_pad, d, y, partial), (d, nb, p, n, n_pad, partial, w, a, meas_k -- may be null),
+        # (d, w1, w, resid, k, n_meas, wbuf, meas), (d, a, x, n_iter, work, resid)
+        'bfhip_ica_tanh': [(0, 4, 2, O, O), (4, 3, 2, O, O), (4, 4, 0, O, O), (4, 4, 2, N, O), (4, 4, 2, O, N)],
+        'bfhip_ica_assemble': [(0, 1, A, 4, 4, A, A, O, N), (2, 0, A, 4, 4, A, A, O, N), (2, 1, A, 0, 4, A, A, O, N), (2, 1, A, 4, 3, A, A, O, N)]
+                              + [tuple(N if i == j else v for i, v in enumerate((2, 1, A, 4, 4, A, A, O, O))) for j in (2, 5, 6, 7)],
+        'bfhip_ica_post': [(0, A, O, A, 0, 2, O, O), (2, A, O, A, -1, 2, O, O), (2, A, O, A, 2, 2, O, O)]
+                          + [tuple(N if i == j else v for i, v in enumerate((2, A, O, A, 0, 2, O, O))) for j in (1, 2, 3, 6, 7)],
+        'bfhip_polar_ns': [(0, A, O, 1, O, O), (1025, A, O, 1, O, O), (2, A, O, -1, O, O)]
+                          + [tuple(N if i == j else v for i, v in enumerate((2, A, O, 1, O, O))) for j in (1, 2, 4, 5)],
     }
     for name, arg_sets in bad.items():
         f = getattr(ctx._lib, name)
