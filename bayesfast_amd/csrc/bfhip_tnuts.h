@@ -1,5 +1,6 @@
 // bfhip_tnuts.h -- launch arguments and helpers shared by the two tempered-NUTS kernels (bfhip_tnuts.hip: the common surrogate at
-// d <= 64 with the diagonal metric; bfhip_tnuts_gen.hip: every other density and metric the NUTS kernels run on).
+// d <= 64 with the diagonal metric; bfhip_tnuts_gen.hip: every other density and metric the NUTS kernels run on) and by their
+// chain driver (bfhip_tnuts_chain.h).  bfhip_tnuts_run fills ONE TnutsArgs, scratch included, for whichever kernel runs.
 #pragma once
 #include <cmath>
 #include "bfhip_common.h"
@@ -16,7 +17,7 @@ struct TnutsArgs {
     uint64_t *rng;
     double *sc, *vec, *tu, *samples, *stats, *stats_t;
     unsigned long long *n_leapfrog;
-    double *scratch;  // [n_chain][4 * TN_MAXL][64] subtree stack vectors
+    double *scratch;  // [n_chain][4 * TN_MAXL][DP] subtree stack vectors (DP: the padded dimension)
     const double *base_S, *base_lin;  // (d,d) symmetric S_b = A_b + A_b^T, (d,)
     double base_c0, logxi;
 };

@@ -14,17 +14,18 @@
 // contracted by the chain's own wave from their compact tables, a point outside the bound of a surrogate with cubic configs takes
 // a second rendezvous at its projection (modules/poly.py:480-503), and the pipeline density adds its two contractions (three more
 // barriers) to the rendezvous, all eight waves sharing them as in the fused NUTS kernel.  The tree logic between two evaluations
-// is each wave's own (the reference's recursion, flattened; draws in its post-order), so a chain reproduces the CPU oracle on the
-// same xoshiro stream.  Built for coverage and parity; the tuned kernel is the one next door.
+// is each wave's own: the chain driver of bfhip_tnuts_chain.h, the same code as under the tuned kernel (the reference's recursion,
+// flattened; draws in its post-order), so a chain reproduces the CPU oracle on the same xoshiro stream.  This file keeps the LDS
+// layout, the rendezvous (matrix-vector products, pipeline contractions), the cubic contractions and the potentials.  Built for
+// coverage and parity; the tuned kernel is the one next door.
 #include <cmath>
 #include "bfhip_common.h"
 #include "bfhip_eval.h"
 #include "bfhip_sampler_defs.h"
 #include "bfhip_wave.h"
 #include "bfhip_oob.h"
-#include "bfhip_metric.h"
 #include "bfhip_pld.h"
-#include "bfhip_tnuts.h"
+#include "bfhip_tnuts_chain.h"
 
 #define TG_WAVES 8
 #define TG_XS 33     // B-operand row: [k = 0 .. 3][chain 0 .. 7] + 1
@@ -441,413 +442,8 @@ __global__ __launch_bounds__(64 * TG_WAVES) void bf_tnuts_gen_kernel(DevModel m,
         }
     };
 
-    if (real) {
-        // ---- chain state ----
-        double *scp = a.sc + (size_t)chain * BFHIP_SC_N;
-        double *vecp = a.vec + (size_t)chain * BFHIP_VEC_N * d;
-        double *sb = a.scratch + (size_t)chain * (4 * TN_MAXL) * DP + lane * E;
-        uint64_t rs[4];
-        for (int k = 0; k < 4; ++k) rs[k] = a.rng[(size_t)chain * 4 + k];
-        double log_step = scp[BFHIP_SC_LOG_STEP], log_bar = scp[BFHIP_SC_LOG_BAR], hbar = scp[BFHIP_SC_HBAR];
-        const double smu = scp[BFHIP_SC_MU];
-        double count = scp[BFHIP_SC_COUNT];
-        double fg_n = scp[BFHIP_SC_FG_N], bg_n = scp[BFHIP_SC_BG_N], n_samples = scp[BFHIP_SC_N_SAMPLES];
-        double prev_upd = scp[BFHIP_SC_PREV_UPDATE], adapt_window = scp[BFHIP_SC_ADAPT_WINDOW];
-        int i_iter = (int)scp[BFHIP_SC_I_ITER], err = (int)scp[BFHIP_SC_ERROR];
-        double qc[E], var[E];
-        auto load_vec = [&](int field, double (&v)[E], double pad) {
-#pragma unroll
-            for (int e = 0; e < E; ++e) v[e] = in[e] ? vecp[field * d + lane * E + e] : pad;
-        };
-        auto store_vec = [&](int field, const double (&v)[E]) {
-#pragma unroll
-            for (int e = 0; e < E; ++e)
-                if (in[e]) vecp[field * d + lane * E + e] = v[e];
-        };
-        load_vec(BFHIP_VEC_Q, qc, 0.);
-        load_vec(BFHIP_VEC_VAR, var, 1.);
-        double u_cur = rfl(a.tu[chain]);
-        unsigned long long nlf = 0;
-        auto uni = [&]() { return bf_u01(bf_xoshiro_next(rs)); };
-        auto logbern = [&](double l) -> bool {  // nuts.py:200-203
-            if (l != l) err = 2;
-            return log(uni()) < l;
-        };
-        const bool lane_ok = lane * E < DP;   // (lanes beyond the padded dimension hold zeros and own no slot words)
-        auto ldv = [&](int slot, double (&v)[E]) {
-#pragma unroll
-            for (int e = 0; e < E; ++e) v[e] = lane_ok ? sb[(size_t)slot * DP + e] : 0.;
-        };
-        auto stv = [&](int slot, const double (&v)[E]) {
-            if (lane_ok) {
-#pragma unroll
-                for (int e = 0; e < E; ++e) sb[(size_t)slot * DP + e] = v[e];
-            }
-        };
-        // velocity of a momentum: metrics.py:88-91 (diagonal), :113-115 (full rank)
-        auto vel = [&](const double (&p)[E], double (&out)[E]) {
-            if constexpr (FULLM) {
-                bf_velocity_full<E>(matp + BF_MAT_COV * msz, p, out, d, lane);
-            } else {
-#pragma unroll
-                for (int e = 0; e < E; ++e) out[e] = var[e] * p[e];
-            }
-        };
-
-        // one tempered leapfrog step from (q, p, u, vt): integration.py:153-222
-        struct TS { double q[E], p[E], v[E]; double u, vt, weight, energy, logp; };
-        auto finish_state = [&](TS &s, double phi, double psi) {
-            double k = 0.;
-#pragma unroll
-            for (int e = 0; e < E; ++e) k += s.p[e] * s.v[e];
-            const double kin = tn_wsum(k);
-            const double ope = 1 + exp(-s.u), beta = 1 / ope, pot = s.u + 2 * log(ope);
-            s.energy = rfl((beta * phi + (1 - beta) * psi + pot) + (0.5 * kin + s.vt * s.vt / 2));
-            s.logp = rfl(-phi);
-            s.weight = rfl(phi - psi);
-        };
-        auto t_step = [&](const TS &s0, double eps) -> TS {
-            TS s = s0;
-            const double dt = 0.5 * eps;
-            double phi, dphi[E], psi, dpsi[E];
-            s.u = rfl(s.u + s.vt * dt);
-#pragma unroll
-            for (int e = 0; e < E; ++e) s.q[e] += dt * s.v[e];
-            potentials(s.q, phi, dphi, psi, dpsi);
-            const double ex = exp(-s.u), beta = 1 / (1 + ex), dbeta = ex * beta * beta, dU = (1 - ex) * beta;
-            s.vt = rfl(s.vt + -(dbeta * (phi - psi) + dU) * eps);
-#pragma unroll
-            for (int e = 0; e < E; ++e) s.p[e] += eps * -(beta * dphi[e] + (1 - beta) * dpsi[e]);
-            s.u = rfl(s.u + s.vt * dt);
-            vel(s.p, s.v);
-#pragma unroll
-            for (int e = 0; e < E; ++e) s.q[e] += dt * s.v[e];
-            potentials(s.q, phi, dphi, psi, dpsi);
-            finish_state(s, phi, psi);
-            return s;
-        };
-        auto dot6 = [&](const double *a0, const double *b0, const double *a1, const double *b1, const double *a2, const double *b2,
-                        const double *a3, const double *b3, const double *a4, const double *b4, const double *a5, const double *b5) -> bool {
-            double r6[6] = {0., 0., 0., 0., 0., 0.};
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                r6[0] += a0[e] * b0[e]; r6[1] += a1[e] * b1[e]; r6[2] += a2[e] * b2[e];
-                r6[3] += a3[e] * b3[e]; r6[4] += a4[e] * b4[e]; r6[5] += a5[e] * b5[e];
-            }
-            wave_sum_n<6>(r6);
-            return (r6[0] <= 0.) || (r6[1] <= 0.) || (r6[2] <= 0.) || (r6[3] <= 0.) || (r6[4] <= 0.) || (r6[5] <= 0.);
-        };
-
-        while (i_iter < a.iter_end && err == 0) {
-            const bool warm = i_iter < a.cfg.n_warmup;
-            // ---- BaseTHMC.astep: base_hmc.py:233-262 ----
-            TS start;
-            {   // p0 = metric.random: one xoshiro draw keys the SplitMix64 stream of the d normals (as in the other kernels)
-                const uint64_t K = bf_xoshiro_next(rs);
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const int dim = lane * E + e;
-                    const uint64_t P = (uint64_t)(dim >> 1);
-                    const double u1 = bf_u01_open0(bf_mix64(K + (2 * P + 1) * BF_GOLDEN)), u2 = bf_u01(bf_mix64(K + (2 * P + 2) * BF_GOLDEN));
-                    const double rad = sqrt(-2. * log(u1));
-                    double sn, cs;
-                    sincospi(2. * u2, &sn, &cs);
-                    const double z = (dim & 1) ? rad * sn : rad * cs;
-                    if constexpr (FULLM) start.p[e] = in[e] ? z : 0.;
-                    else start.p[e] = in[e] ? (1. / sqrt(var[e])) * z : 0.;
-                    start.q[e] = qc[e];
-                }
-                if constexpr (FULLM) bf_solve_lt<E>(matp + BF_MAT_CHOL_ROWS * msz, start.p, d, lane);  // metrics.py:123-127
-            }
-            {   // v0 = rng.normal(0, 1): a stream of its own, first (cosine) element
-                const uint64_t K = bf_xoshiro_next(rs);
-                const double u1 = bf_u01_open0(bf_mix64(K + BF_GOLDEN)), u2 = bf_u01(bf_mix64(K + 2 * BF_GOLDEN));
-                double sn, cs;
-                sincospi(2. * u2, &sn, &cs);
-                start.vt = rfl(sqrt(-2. * log(u1)) * cs);
-            }
-            start.u = u_cur;
-            vel(start.p, start.v);
-            {
-                double phi, dphi[E], psi, dpsi[E];
-                potentials(start.q, phi, dphi, psi, dpsi);
-                finish_state(start, phi, psi);
-            }
-            if (!(fabs(start.energy) <= 1.7976931348623157e308)) { err = 1; break; }
-            const double eps0 = rfl(exp(warm ? log_step : log_bar));
-            // ---- Tree.__init__: nuts.py:24-43 ----
-            TS left = start, right = start;
-            double prop_q[E], p_sum[E];
-#pragma unroll
-            for (int e = 0; e < E; ++e) { prop_q[e] = start.q[e]; p_sum[e] = start.p[e]; }
-            double prop_u = start.u, prop_w = start.weight, prop_E = start.energy, prop_logp = start.logp;
-            double log_size = 0., accept_sum = 0., max_de = 0.;
-            int depth = 0, n_prop = 0, diverging = 0, turning = 0;
-            for (int it = 0; it < a.cfg.max_treedepth && err == 0; ++it) {
-                const int dir = logbern(-0.6931471805599453094) ? 1 : -1;  // nuts.py:210
-                const double eps = dir > 0 ? eps0 : -eps0;
-                const TS old_left = left, old_right = right;
-                // ---- _build_subtree(edge, depth, eps), recursion flattened: leaf i merges upwards while bit `lev` of i is set ----
-                TS cur = dir > 0 ? right : left;
-                double T_lp[E], T_ps[E], T_pq[E], L0_lp[E], L0_rp[E], L0_ps[E], L0_pq[E];
-#pragma unroll
-                for (int e = 0; e < E; ++e) { T_lp[e] = T_ps[e] = T_pq[e] = L0_lp[e] = L0_rp[e] = L0_ps[e] = L0_pq[e] = 0.; }
-                double T_pu = 0., T_pw = 0., T_pE = 0., T_plogp = 0., T_ls = 0., T_acc = 0.;
-                double sub_acc = 0.;
-                long sub_n = 0;
-                bool done = false;
-                const int n_leaf = 1 << depth;
-                for (int i_leaf = 0; i_leaf < n_leaf && !done; ++i_leaf) {
-                    // ---- _single_step: nuts.py:105-132 ----
-                    const TS nxt = t_step(cur, eps);
-                    nlf += 1;
-                    sub_n += 1;
-                    double dE = rfl(nxt.energy - start.energy);
-                    if (dE != dE) dE = INFINITY;
-                    if (fabs(dE) > fabs(max_de)) max_de = dE;
-                    if (!(fabs(dE) < a.cfg.max_change)) {
-                        diverging = 1;
-                        // the stub subtree: ancestors still add their left halves' accept sums (nuts.py:173)
-                        for (int al = 0; al < depth; ++al)
-                            if ((i_leaf >> al) & 1) sub_acc = rfl(sub_acc + lsw[al * TS_N + TS_ACC]);
-                        done = true;
-                        break;
-                    }
-                    cur = nxt;
-#pragma unroll
-                    for (int e = 0; e < E; ++e) { T_lp[e] = nxt.p[e]; T_ps[e] = nxt.p[e]; T_pq[e] = nxt.q[e]; }
-                    T_pu = nxt.u; T_pw = nxt.weight; T_pE = nxt.energy; T_plogp = nxt.logp;
-                    T_ls = -dE;
-                    { const double pa = rfl(exp(-dE)); T_acc = pa > 1. ? 1. : pa; }
-                    int lev = 0;
-                    bool abort = false;
-                    while (lev < depth && ((i_leaf >> lev) & 1)) {
-                        // ---- merge with the waiting left sibling of this level: nuts.py:146-178 ----
-                        double A_lp[E], A_rp[E], A_ps[E], A_pq[E];
-                        if (lev == 0) {
-#pragma unroll
-                            for (int e = 0; e < E; ++e) { A_lp[e] = L0_lp[e]; A_rp[e] = L0_rp[e]; A_ps[e] = L0_ps[e]; A_pq[e] = L0_pq[e]; }
-                        } else {
-                            ldv(4 * lev + 0, A_lp); ldv(4 * lev + 1, A_rp); ldv(4 * lev + 2, A_ps); ldv(4 * lev + 3, A_pq);
-                        }
-                        const double *ls = lsw + lev * TS_N;
-                        double psum[E];
-#pragma unroll
-                        for (int e = 0; e < E; ++e) psum[e] = A_ps[e] + T_ps[e];
-                        bool turn;
-                        if (lev >= 1) {  // with the sub-span checks for depth > 1 (nuts.py:154-161): six sums, one reduction
-                            double A_lv[E], A_rv[E], T_lv[E], ps1[E], ps2[E];
-                            if constexpr (FULLM) bf_velocity_full3<E>(matp + BF_MAT_COV * msz, A_lp, A_rp, T_lp, A_lv, A_rv, T_lv, d, lane);
-                            else { vel(A_lp, A_lv); vel(A_rp, A_rv); vel(T_lp, T_lv); }
-#pragma unroll
-                            for (int e = 0; e < E; ++e) { ps1[e] = A_ps[e] + T_lp[e]; ps2[e] = A_rp[e] + T_ps[e]; }
-                            turn = dot6(psum, A_lv, psum, cur.v, ps1, A_lv, ps1, T_lv, ps2, A_rv, ps2, cur.v);
-                        } else {
-                            double A_lv[E];
-                            vel(A_lp, A_lv);
-                            double r2[2] = {0., 0.};
-#pragma unroll
-                            for (int e = 0; e < E; ++e) { r2[0] += psum[e] * A_lv[e]; r2[1] += psum[e] * cur.v[e]; }
-                            wave_sum_n<2>(r2);
-                            turn = (r2[0] <= 0.) || (r2[1] <= 0.);
-                        }
-                        const double acc_l = rfl(ls[TS_ACC]), ls_l = rfl(ls[TS_LS]);
-                        const double ls_new = rfl(tn_logaddexp(ls_l, T_ls));
-                        const bool take2 = logbern(T_ls - ls_new);  // :164 (drawn even when this merge turns)
-                        T_acc = rfl(acc_l + T_acc);
-                        if (turn) {
-                            for (int al = lev + 1; al < depth; ++al)
-                                if ((i_leaf >> al) & 1) T_acc = rfl(T_acc + lsw[al * TS_N + TS_ACC]);
-                            abort = true;
-                            turning = 1;
-                            break;
-                        }
-                        if (!take2) {
-#pragma unroll
-                            for (int e = 0; e < E; ++e) T_pq[e] = A_pq[e];
-                            T_pE = rfl(ls[TS_E]); T_plogp = rfl(ls[TS_LOGP]); T_pu = rfl(ls[TS_U]); T_pw = rfl(ls[TS_W]);
-                        }
-                        T_ls = ls_new;
-#pragma unroll
-                        for (int e = 0; e < E; ++e) { T_ps[e] = psum[e]; T_lp[e] = A_lp[e]; }
-                        lev += 1;
-                    }
-                    if (abort) { sub_acc = T_acc; done = true; break; }
-                    if (lev < depth) {
-                        // wait for the right sibling
-                        if (lev == 0) {
-#pragma unroll
-                            for (int e = 0; e < E; ++e) { L0_lp[e] = T_lp[e]; L0_rp[e] = cur.p[e]; L0_ps[e] = T_ps[e]; L0_pq[e] = T_pq[e]; }
-                        } else {
-                            stv(4 * lev + 0, T_lp); stv(4 * lev + 1, cur.p); stv(4 * lev + 2, T_ps); stv(4 * lev + 3, T_pq);
-                        }
-                        double *ls = lsw + lev * TS_N;
-                        if (lane == 0) { ls[TS_LS] = T_ls; ls[TS_ACC] = T_acc; ls[TS_E] = T_pE; ls[TS_LOGP] = T_plogp; ls[TS_U] = T_pu; ls[TS_W] = T_pw; }
-                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                    } else {
-                        sub_acc = T_acc;  // the whole subtree of this doubling is complete
-                    }
-                }
-                depth += 1;
-                accept_sum = rfl(accept_sum + sub_acc);
-                n_prop += (int)sub_n;
-                if (err) break;
-                if (diverging || turning) break;   // Tree.extend returns before touching the ends' p_sum (nuts.py:71-73)
-                // ---- Tree.extend after a complete subtree: nuts.py:75-103 ----
-                if (dir > 0) right = cur; else left = cur;
-                if (logbern(T_ls - log_size)) {
-#pragma unroll
-                    for (int e = 0; e < E; ++e) prop_q[e] = T_pq[e];
-                    prop_u = T_pu; prop_w = T_pw; prop_E = T_pE; prop_logp = T_plogp;
-                }
-                log_size = rfl(tn_logaddexp(log_size, T_ls));
-#pragma unroll
-                for (int e = 0; e < E; ++e) p_sum[e] += T_ps[e];  // :86 (in place: the aliases below see the new value)
-                bool turn;
-                {
-                    // leftmost / rightmost halves: nuts.py:56-69 (the first leaf of the new subtree has momentum T_lp, the last is cur)
-                    double T_lv[E], t1[E], t2[E];
-                    vel(T_lp, T_lv);
-                    double lm_begin_v[E], lm_end_p[E], lm_end_v[E], rm_begin_p[E], rm_begin_v[E], rm_end_v[E], lm_ps[E], rm_ps[E];
-#pragma unroll
-                    for (int e = 0; e < E; ++e) {
-                        lm_begin_v[e] = dir > 0 ? old_left.v[e] : cur.v[e];
-                        lm_end_p[e] = dir > 0 ? old_right.p[e] : T_lp[e];
-                        lm_end_v[e] = dir > 0 ? old_right.v[e] : T_lv[e];
-                        rm_begin_p[e] = dir > 0 ? T_lp[e] : old_left.p[e];
-                        rm_begin_v[e] = dir > 0 ? T_lv[e] : old_left.v[e];
-                        rm_end_v[e] = dir > 0 ? cur.v[e] : old_right.v[e];
-                        lm_ps[e] = dir > 0 ? p_sum[e] : T_ps[e];
-                        rm_ps[e] = dir > 0 ? T_ps[e] : p_sum[e];
-                    }
-#pragma unroll
-                    for (int e = 0; e < E; ++e) { t1[e] = lm_ps[e] + rm_begin_p[e]; t2[e] = lm_end_p[e] + rm_ps[e]; }
-                    turn = dot6(p_sum, left.v, p_sum, right.v, t1, lm_begin_v, t1, rm_begin_v, t2, lm_end_v, t2, rm_end_v);
-                }
-                turning = turn ? 1 : 0;
-                if (turning) break;
-            }
-            if (err) break;
-            // ---- iteration end: base_hmc.py:252-262 ----
-            const double accept_stat = accept_sum / (double)n_prop;
-            if (warm && a.cfg.adapt_step_size) {  // step_size.py:31-45
-                const double wgt = 1. / (count + a.cfg.t_0);
-                hbar = ((1. - wgt) * hbar + wgt * (a.cfg.target_accept - accept_stat));
-                log_step = smu - hbar * sqrt(count) / a.cfg.gamma;
-                const double mk = exp(-a.cfg.k * log(count));
-                log_bar = mk * log_step + (1. - mk) * log_bar;
-                count += 1.;
-            }
-#pragma unroll
-            for (int e = 0; e < E; ++e) qc[e] = prop_q[e];
-            u_cur = prop_u;
-            const int orow = i_iter - a.iter_out0;
-            if (orow >= 0 && orow < a.n_out) {
-                if (lane == 0) {
-                    double *st = a.stats + ((size_t)chain * a.n_out + orow) * BFHIP_STAT_STRIDE;
-                    st[BFHIP_NS_LOGP] = prop_logp;
-                    st[BFHIP_NS_ENERGY] = prop_E;
-                    st[BFHIP_NS_TREE_DEPTH] = (double)depth;
-                    st[BFHIP_NS_TREE_SIZE] = (double)n_prop;
-                    st[BFHIP_NS_MEAN_TREE_ACCEPT] = accept_stat;
-                    st[BFHIP_NS_STEP_SIZE] = exp(log_step);
-                    st[BFHIP_NS_STEP_SIZE_BAR] = exp(log_bar);
-                    st[BFHIP_NS_WARMUP] = warm ? 1. : 0.;
-                    st[BFHIP_NS_ENERGY_CHANGE] = prop_E - start.energy;
-                    st[BFHIP_NS_MAX_ENERGY_CHANGE] = max_de;
-                    st[BFHIP_NS_DIVERGING] = (double)diverging;
-                    double *tt = a.stats_t + ((size_t)chain * a.n_out + orow) * 2;
-                    tt[0] = prop_u;
-                    tt[1] = (prop_w == 0) ? 1. : prop_w / expm1(prop_w);
-                }
-#pragma unroll
-                for (int e = 0; e < E; ++e)
-                    if (in[e]) a.samples[((size_t)chain * a.n_out + orow) * d + lane * E + e] = qc[e];
-            }
-            if (warm && a.cfg.adapt_metric) {
-                const long delta = (long)(n_samples - prev_upd);
-                if constexpr (FULLM) {
-                    // QuadMetricFullAdapt.update: metrics.py:294-324, _WeightedCovariance.add_sample :401-407 (as in bfhip_sampler.hip)
-                    double fm[E], bm[E], od[E], nd[E];
-                    load_vec(BFHIP_VEC_FG_MEAN, fm, 0.);
-                    load_vec(BFHIP_VEC_BG_MEAN, bm, 0.);
-                    double *fgT = matp + BF_MAT_FG * msz, *bgT = matp + BF_MAT_BG * msz, *covT = matp + BF_MAT_COV * msz;
-                    fg_n += 1.;
-#pragma unroll
-                    for (int e = 0; e < E; ++e) { od[e] = qc[e] - fm[e]; fm[e] += od[e] / fg_n; nd[e] = qc[e] - fm[e]; }
-                    const bool refresh = (delta + 1) % (long)a.cfg.update_window == 0;   // _update_from_weightvar: :287-292
-                    bf_welford_cov<E>(fgT, nd, od, d, lane, refresh ? covT : nullptr, fg_n);
-                    bg_n += 1.;
-#pragma unroll
-                    for (int e = 0; e < E; ++e) { od[e] = qc[e] - bm[e]; bm[e] += od[e] / bg_n; nd[e] = qc[e] - bm[e]; }
-                    bf_welford_cov<E>(bgT, nd, od, d, lane);
-                    if (refresh) {
-                        double *wT = matp + BF_MAT_WORK * msz;
-                        if (bf_chol_rows<E>(covT, wT, d, lane))
-                            bf_chol_publish<E>(wT, matp + BF_MAT_CHOL * msz, matp + BF_MAT_CHOL_ROWS * msz, d, lane);
-                    }
-                    if ((double)delta >= adapt_window) {
-                        for (int j = 0; j < d; ++j) {
-#pragma unroll
-                            for (int e = 0; e < E; ++e) {
-                                const int i = lane * E + e;
-                                if (i < d) {
-                                    fgT[(size_t)j * d + i] = bgT[(size_t)j * d + i];
-                                    bgT[(size_t)j * d + i] = (i == j) ? 10. : 0.;  // _WeightedCovariance(n): 10 I
-                                }
-                            }
-                        }
-#pragma unroll
-                        for (int e = 0; e < E; ++e) { fm[e] = bm[e]; bm[e] = 0.; }
-                        fg_n = bg_n; bg_n = 10.; prev_upd = n_samples;
-                        if (a.cfg.doubling) adapt_window *= 2.;
-                    }
-                    n_samples += 1.;
-                    store_vec(BFHIP_VEC_FG_MEAN, fm);
-                    store_vec(BFHIP_VEC_BG_MEAN, bm);
-                } else {
-                    // QuadMetricDiagAdapt.update: metrics.py:186-211
-                    double fm[E], fr[E], bm[E], br[E];
-                    load_vec(BFHIP_VEC_FG_MEAN, fm, 0.); load_vec(BFHIP_VEC_FG_RAW, fr, 0.);
-                    load_vec(BFHIP_VEC_BG_MEAN, bm, 0.); load_vec(BFHIP_VEC_BG_RAW, br, 0.);
-                    fg_n += 1.; bg_n += 1.;
-#pragma unroll
-                    for (int e = 0; e < E; ++e) {
-                        double od = qc[e] - fm[e]; fm[e] += od / fg_n; fr[e] += 1. * od * (qc[e] - fm[e]);
-                        od = qc[e] - bm[e]; bm[e] += od / bg_n; br[e] += 1. * od * (qc[e] - bm[e]);
-                    }
-                    if ((delta + 1) % (long)a.cfg.update_window == 0) {
-#pragma unroll
-                        for (int e = 0; e < E; ++e)
-                            if (in[e]) var[e] = fr[e] / fg_n;
-                        store_vec(BFHIP_VEC_VAR, var);
-                    }
-                    if ((double)delta >= adapt_window) {
-#pragma unroll
-                        for (int e = 0; e < E; ++e) { fm[e] = bm[e]; fr[e] = br[e]; bm[e] = 0.; br[e] = 0.; }
-                        fg_n = bg_n; bg_n = 10.; prev_upd = n_samples;
-                        if (a.cfg.doubling) adapt_window *= 2.;
-                    }
-                    n_samples += 1.;
-                    store_vec(BFHIP_VEC_FG_MEAN, fm); store_vec(BFHIP_VEC_FG_RAW, fr);
-                    store_vec(BFHIP_VEC_BG_MEAN, bm); store_vec(BFHIP_VEC_BG_RAW, br);
-                }
-            }
-            i_iter += 1;
-        }
-        // ---- write the chain state back ----
-        store_vec(BFHIP_VEC_Q, qc);
-        if (lane == 0) {
-            for (int k = 0; k < 4; ++k) a.rng[(size_t)chain * 4 + k] = rs[k];
-            scp[BFHIP_SC_LOG_STEP] = log_step; scp[BFHIP_SC_LOG_BAR] = log_bar; scp[BFHIP_SC_HBAR] = hbar; scp[BFHIP_SC_COUNT] = count;
-            scp[BFHIP_SC_FG_N] = fg_n; scp[BFHIP_SC_BG_N] = bg_n; scp[BFHIP_SC_N_SAMPLES] = n_samples;
-            scp[BFHIP_SC_PREV_UPDATE] = prev_upd; scp[BFHIP_SC_ADAPT_WINDOW] = adapt_window;
-            scp[BFHIP_SC_I_ITER] = (double)i_iter; scp[BFHIP_SC_ERROR] = (double)err;
-            a.tu[chain] = u_cur;
-            if (a.n_leapfrog && nlf) atomicAdd(a.n_leapfrog, nlf);
-        }
-    }
+    // the chain itself (bfhip_tnuts_chain.h); it returns here whatever ends it
+    if (real) tn_run_chain<DP, FULLM>(a, chain, lane, lsw, matp, potentials);
     // the chains of this wave's workgroup that are still running need its matvec jobs, its share of the contractions and the barriers
     {
         double z[E], t0[E], t1[E], t2[E], t3[E];
@@ -873,22 +469,15 @@ static int tg_launch_t(bfhip_ctx *ctx, const TnutsArgs &a, const double *mat) {
     return 0;
 }
 
-int bf_tnuts_gen_launch(bfhip_ctx *ctx, const TnutsArgs &a_in, const double *mat) {
-    const DevModel &m = ctx->model;
-    TnutsArgs a = a_in;
-    const int DP = m.DP;
-    // the subtree stack: 4 TN_MAXL vector slots of DP doubles per chain
-    const size_t need = (size_t)((a.n_chain + 15) / 16 * 16) * (4 * TN_MAXL) * DP * sizeof(double);
-    if (int rc = bf_grow(ctx, &ctx->scratch, &ctx->scratch_bytes, need)) return rc;
-    a.scratch = (double *)ctx->scratch;
+int bf_tnuts_gen_launch(bfhip_ctx *ctx, const TnutsArgs &a, const double *mat) {
     const bool full = mat != NULL;
 #define TG_PICK(Wv) (full ? tg_launch_t<Wv, true>(ctx, a, mat) : tg_launch_t<Wv, false>(ctx, a, mat))
-    switch (DP) {
+    switch (ctx->model.DP) {
     case 16: return TG_PICK(1);
     case 32: return TG_PICK(2);
     case 64: return TG_PICK(4);
     case 128: return TG_PICK(8);
     }
 #undef TG_PICK
-    return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_tnuts_run: padded dimension %d", DP);
+    return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_tnuts_run: padded dimension %d", ctx->model.DP);
 }

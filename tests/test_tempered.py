@@ -208,19 +208,24 @@ def test_sample_tnuts_on_a_bounded_density_with_decay():
 
 # ---- round 6: the generic tempered kernel (bfhip_tnuts_gen.hip) -- TNUTS on everything NUTS runs on ----
 
-def _tnuts_against_oracle(spec, x0, u0, base_mean, base_cov, logxi, n_iter, n_warmup, seed, chains, head=6, metric=None, tol=1e-8):
-    """Run the device's TNUTS and the oracle's on shared xoshiro streams; discrete fields exactly, the head of the run closely."""
+def _tnuts_against_oracle(spec, x0, u0, base_mean, base_cov, logxi, n_iter, n_warmup, seed, chains, head=6, metric=None, tol=1e-8,
+                          ref=None, **run_kw):
+    """Run the device's TNUTS and the oracle's on shared xoshiro streams; discrete fields exactly, the head of the run closely.
+    ``run_kw`` (max_treedepth, max_change) goes to both; ``ref``: the oracle's (samples, stats) per chain, when the caller has them."""
     from oracle import oracle as orc
     from bayesfast_amd.device import get_context, DeviceDensity
     from bayesfast_amd.chains import DeviceChains
     from bayesfast_amd import _lib
     base = orc.gaussian_base_spec(base_mean, base_cov)
     dc = DeviceChains(DeviceDensity(spec, get_context(0)), x0, seed=seed, metric=metric)
-    s, st, stt = dc.run_tempered(n_iter, base_mean, base_cov, logxi=logxi, u_0=u0, n_warmup=n_warmup)
+    s, st, stt = dc.run_tempered(n_iter, base_mean, base_cov, logxi=logxi, u_0=u0, n_warmup=n_warmup, **run_kw)
     s, st, stt = s.cpu().numpy(), st.cpu().numpy(), stt.cpu().numpy()
     for i in chains:
-        ch = orc.Chain(x0[i]) if metric is None else orc.Chain(x0[i], metric=np.eye(x0.shape[1]) if isinstance(metric, str) else metric)
-        so, sto, _ = orc.tnuts_run(spec, base, logxi, ch, orc.make_rng('xoshiro', seed=seed, stream=i), u0[i], n_iter, n_warmup)
+        if ref is not None:
+            so, sto = ref[i]
+        else:
+            ch = orc.Chain(x0[i]) if metric is None else orc.Chain(x0[i], metric=np.eye(x0.shape[1]) if isinstance(metric, str) else metric)
+            so, sto, _ = orc.tnuts_run(spec, base, logxi, ch, orc.make_rng('xoshiro', seed=seed, stream=i), u0[i], n_iter, n_warmup, **run_kw)
         for f in ('tree_depth', 'tree_size', 'diverging'):
             assert np.array_equal(st[i, :, _lib.NSTATS.index(f)], sto[f]), (i, f, st[i, :, _lib.NSTATS.index(f)], sto[f])
         np.testing.assert_allclose(s[i, :head], so[:head], rtol=tol, atol=tol)
@@ -294,6 +299,16 @@ def test_device_tnuts_on_cubic_scaled_and_linked_surrogates_matches_oracle(cubic
 @pytest.mark.parametrize('cubic', [0, 1])
 def test_device_tnuts_at_128_dimensions_matches_oracle(cubic):
     """d = 128 (two elements per lane, the A fragments streamed from L2), plain and with config 5's cubic configs on 16 inputs."""
+    spec, P, rng = _spec_128(cubic)
+    d = 128
+    n_chain = 9
+    x0 = rng.normal(size=(n_chain, d)) * 0.5 / np.sqrt(np.diag(P))
+    u0 = rng.normal(size=n_chain)
+    _tnuts_against_oracle(spec, x0, u0, np.zeros(d), np.diag(1.3 / np.diag(P)), 0., 8, 5, 52, (0, 8), head=4)
+
+
+def _spec_128(cubic):
+    """The 128-d surrogate of the test above (and its precision matrix, and the generator, for the starting points)."""
     from oracle import oracle as orc
     d = 128
     rng = np.random.default_rng(128 + cubic)
@@ -316,11 +331,7 @@ def test_device_tnuts_at_128_dimensions_matches_oracle(cubic):
     poly = dict(input_size=d, output_size=1, configs=cfgs, use_bound=False)
     xs = rng.normal(size=(6 * d, d)) / np.sqrt(np.diag(P))
     poly.update(orc.set_bound(poly, xs, -0.5 * np.einsum('ij,jk,ik->i', xs, P, xs), dict(alpha_p=70.)))
-    spec = dict(d=d, poly=poly)
-    n_chain = 9
-    x0 = rng.normal(size=(n_chain, d)) * 0.5 / np.sqrt(np.diag(P))
-    u0 = rng.normal(size=n_chain)
-    _tnuts_against_oracle(spec, x0, u0, np.zeros(d), np.diag(1.3 / np.diag(P)), 0., 8, 5, 52, (0, 8), head=4)
+    return dict(d=d, poly=poly), P, rng
 
 
 @pytest.mark.gpu
@@ -367,3 +378,96 @@ def test_device_tnuts_on_the_des_shaped_pipeline_matches_oracle():
         x0 = np.concatenate([x0, x0[:1] + 0.05 * rng.normal(size=(3, d))])
         u0 = rng.normal(size=x0.shape[0])
         _tnuts_against_oracle(spec, x0, u0, x0.mean(0), np.eye(d) * 0.05, 0., 8, 5, 91, (0, 4), head=4, tol=1e-7)
+
+
+# ---- the chain driver shared by the two kernels (bfhip_tnuts_chain.h): state write-back, windows, depth limit, divergences ----
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('kernel', ['tuned', 'generic', 'd128', 'full'])
+def test_tnuts_launch_cut_never_changes_results(kernel):
+    """Where a run is cut into launches changes nothing: 20 iterations at once against 7 + 13 from the same start are EQUAL in
+    samples, statistics, u and weights, and so are 3 more iterations from both end states (the state written back, the random
+    streams, the metric's vectors and matrices).  adapt_window = 5 puts the metric's window switch and the doubling inside the 12
+    warm-up iterations.  The tuned kernel at d = 24, the generic one forced onto the same density, d = 128 (two elements per
+    lane, 9 chains), and the full-rank metric while adapting at d = 12; 19 chains are ragged for 4 and 8 per workgroup."""
+    from bayesfast_amd.device import get_context, DeviceDensity
+    from bayesfast_amd.chains import DeviceChains
+    from bayesfast_amd.workloads import correlated_gaussian_spec
+    from bayesfast_amd import _lib
+    rng = np.random.default_rng(40)
+    metric, n_chain, logxi = None, 19, 0.2
+    if kernel == 'd128':
+        spec, P, _ = _spec_128(0)
+        d, n_chain, logxi = 128, 9, 0.
+        sd = 1. / np.sqrt(np.diag(P))
+        x0, base_cov = rng.normal(size=(n_chain, d)) * 0.5 * sd, np.diag(1.3 * sd**2)
+    else:
+        d = 12 if kernel == 'full' else 24
+        spec, cov = correlated_gaussian_spec(d, fit_scale=1.5)
+        x0, base_cov = rng.normal(size=(n_chain, d)) * 0.3, np.eye(d) * 1.5
+        if kernel == 'full':
+            metric = cov * 0.9
+    u0 = rng.normal(size=n_chain)
+    dens = DeviceDensity(spec, get_context(0))
+
+    def run(cuts):
+        dc = DeviceChains(dens, x0, seed=33, metric=metric, adapt_window=5)
+        parts = [[t.cpu().numpy() for t in dc.run_tempered(n, np.zeros(d), base_cov, logxi=logxi, u_0=u0, n_warmup=12)] for n in cuts]
+        more = [t.cpu().numpy() for t in dc.run_tempered(3, np.zeros(d), base_cov, logxi=logxi, n_warmup=12)]
+        return [np.concatenate(x, 1) for x in zip(*parts)], more
+    try:
+        _lib.debug_set('tnuts_generic', int(kernel == 'generic'))
+        whole, whole_more = run((20,))
+        cut, cut_more = run((7, 13))
+    finally:
+        _lib.debug_set('tnuts_generic', 0)
+    assert whole[1][:, :12, _lib.NSTATS.index('warmup')].all() and np.isfinite(whole[0]).all()
+    for a, b in zip(whole + whole_more, cut + cut_more):
+        assert np.array_equal(a, b)
+
+
+_DEPTH_LIMIT = dict(d=12, n_chain=11, n_iter=16, n_warmup=10, seed=119, chains=(0, 3, 10), logxi=0.3,
+                    run_kw=dict(max_treedepth=3, max_change=50.))
+
+
+@pytest.fixture(scope='module')
+def depth_limit_ref():
+    """The oracle's side of the test below, once for both kernels: spec, starting points and (samples, stats) per compared chain."""
+    from oracle import oracle as orc
+    from bayesfast_amd.workloads import correlated_gaussian_spec
+    c = _DEPTH_LIMIT
+    d = c['d']
+    spec = dict(correlated_gaussian_spec(d, fit_scale=1.5)[0])
+    rng = np.random.default_rng(5)
+    x0, u0 = rng.normal(size=(c['n_chain'], d)) * 0.3, rng.normal(size=c['n_chain'])
+    base = orc.gaussian_base_spec(np.zeros(d), np.eye(d) * 1.5)
+    ref = {}
+    for i in c['chains']:
+        so, sto, _ = orc.tnuts_run(spec, base, c['logxi'], orc.Chain(x0[i]), orc.make_rng('xoshiro', seed=c['seed'], stream=i), u0[i],
+                                   c['n_iter'], c['n_warmup'], **c['run_kw'])
+        ref[i] = (so, sto)
+    return spec, x0, u0, ref
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('generic', [0, 1])
+def test_device_tnuts_depth_limit_and_divergences_match_oracle(depth_limit_ref, generic):
+    """max_treedepth = 3 and max_change = 50 on the 12-d correlated Gaussian: trees that end at the depth limit, by a divergence
+    (the stub subtree whose ancestors still add their accept sums) and by a U-turn inside a subtree, on the tuned and on the
+    forced generic kernel, against the oracle on shared streams.  Over the compared chains (0, 3, 10) the oracle has 3 diverging
+    iterations, 34 at the depth limit without divergence and 1 with tree_size < 2^depth - 1 without divergence (chain 3, iteration
+    9: 5 leaves at depth 3).  An inner U-turn at depth <= 3 needs steps so long that a smaller max_change turns it into a divergence:
+    50 is the smallest of the values tried on the oracle (0.05 .. 100, 200 to 300 seeds each) at which one survives."""
+    from bayesfast_amd import _lib
+    c = _DEPTH_LIMIT
+    spec, x0, u0, ref = depth_limit_ref
+    dv = np.concatenate([r[1]['diverging'] for r in ref.values()]) == 1
+    td = np.concatenate([r[1]['tree_depth'] for r in ref.values()])
+    ts = np.concatenate([r[1]['tree_size'] for r in ref.values()])
+    assert dv.any() and (~dv & (td == 3)).any() and (~dv & (ts < 2**td - 1)).any()
+    try:
+        _lib.debug_set('tnuts_generic', generic)
+        _tnuts_against_oracle(spec, x0, u0, np.zeros(c['d']), np.eye(c['d']) * 1.5, c['logxi'], c['n_iter'], c['n_warmup'], c['seed'],
+                              c['chains'], ref=ref, **c['run_kw'])
+    finally:
+        _lib.debug_set('tnuts_generic', 0)
