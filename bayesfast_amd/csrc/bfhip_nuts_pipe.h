@@ -70,6 +70,21 @@ template <> struct PipeAcc<2> { typedef d2_t type; };
 __device__ inline d4_t bf_pipe_mfma(double a_, double b_, d4_t c_) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a_, b_, c_, 0, 0, 0); }
 __device__ inline double bf_pipe_mfma(double a_, double b_, double c_) { return __builtin_amdgcn_mfma_f64_4x4x4f64(a_, b_, c_, 0, 0, 0); }
 
+// bf_u01 of a 64-bit draw, (x >> 11) * 2^-53, from the bit patterns of two doubles: with n = x >> 11 = hi * 2^32 + lo (hi < 2^21),
+// 2^31 + hi * 2^-21 and 1/2 + lo * 2^-53 are doubles whose mantissa fields hold hi and lo as they stand; the first minus
+// (2^31 + 1/2) is a multiple of 2^-21 below 1 in magnitude, and its sum with the second is n * 2^-53 < 1, a multiple of 2^-53:
+// both operations are exact, the result is bf_u01's to the last bit (two FP64 additions for a conversion of five instructions).
+__device__ inline double bf_pipe_u01(uint64_t x) {
+    const uint64_t n = x >> 11;
+    const double hi = __longlong_as_double((long long)(0x41E0000000000000ull | (n >> 32)));
+    const double lo = __longlong_as_double((long long)(0x3FE0000000000000ull | (n & 0xffffffffull)));
+    return (hi - 2147483648.5) + lo;
+}
+// -v by its sign bit: on wave-uniform values scalar instructions, where the FP64 negation would be a vector one
+__device__ inline double bf_pipe_neg(double v) { return __longlong_as_double(__double_as_longlong(v) ^ (long long)0x8000000000000000ull); }
+// the direction of a doubling, bf_u01(x) < 0.5 ? 1 : -1 (nuts.py:210): (x >> 11) * 2^-53 < 1/2 exactly when bit 63 of x is clear
+__device__ inline int bf_pipe_dir(uint64_t x) { return (x >> 63) ? -1 : 1; }
+
 template <int W, bool TR, int DEC = 0, int QUAD = 0>
 __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerArgs a) {
     using G = SamplerGeo<W>;
@@ -131,7 +146,7 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
     double TPg = 0., L0g = 0.;            // the gradient at the proposals TPq / L0q (the next iteration may start there)
     uint64_t rs[4] = {0, 0, 0, 0};
     int i_iter = 0, mode = M_DONE, err = 0;
-    double eps = 0., eps_t = 0.;
+    double eps_t = 0., heps_t = 0.;  // the signed step of the doubling under way and its half: set where a tree starts, negated where a doubling turns
     int dir = 1, depth = 0, i_leaf = 0, n_prop = 0, diverged = 0;
     double start_energy = 0., acc_sum = 0.;
     double T_W = 0., T_acc = 0.;
@@ -225,8 +240,10 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
             depth = 0; acc_sum = 0.; n_prop = 0; diverged = 0; i_leaf = 0;
             // step_size.py:25-29: exp(log_step) while warming up, exp(log_step_bar) after; both are kept up to date for the
             // statistics (CS_STEP_NOW / CS_STEP_BAR), so no exponential is needed here
-            eps = (i_iter < nw) ? cs_get(CS_STEP_NOW) : cs_get(CS_STEP_BAR);
-            dir = (bf_u01(bf_xoshiro_next(rs)) < 0.5) ? 1 : -1;  // nuts.py:210, log(U) < log(1/2)
+            const double eps = (i_iter < nw) ? cs_get(CS_STEP_NOW) : cs_get(CS_STEP_BAR);
+            dir = bf_pipe_dir(bf_xoshiro_next(rs));  // nuts.py:210, log(U) < log(1/2)
+            eps_t = dir > 0 ? eps : bf_pipe_neg(eps);  // eps * (double)dir
+            heps_t = rfl(0.5 * eps_t);
             pend = false;
             mode = M_LEAF;
         }
@@ -353,12 +370,15 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
 #endif
         TRACE(0);
         // ================= phase A: first half of the (speculative) leapfrog step, B operands =================
-        bool evaluating = false;
+        // (the chain state q, p, g changes at ONE place ahead of the step, the block under `turn` below: assigned inside the branches
+        // that decide it, every way out of them carried a copy of the three vectors to the registers of the step)
+        bool evaluating = false, turn = false;
+        int eo2 = 0;
         if (mode == M_INIT) {
-            evaluating = true;  // compute_state at the start of a launch (base_hmc.py:70): a step of length 0
-            eps_t = 0.;
+            // compute_state at the start of a launch (base_hmc.py:70): a step of length 0.  (Only a launch's first trip finds this
+            // mode -- an iteration's end goes through init_tree in the same pass -- so eps_t and heps_t are still 0.)
+            evaluating = true;
         } else if (mode == M_LEAF) {
-            int dir_use = dir;
             evaluating = true;
             if (pend && i_leaf == (1 << depth) - 1) {
                 // the leaf in flight closes its doubling: park the new end (its p waits in TRp until the pending
@@ -371,18 +391,21 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
                 } else {
                     uint64_t t[4] = {rs[0], rs[1], rs[2], rs[3]};
                     for (int k = 0; k <= depth; ++k) (void)bf_xoshiro_next(t);  // `depth` merges and the swap
-                    dir_use = (bf_u01(bf_xoshiro_next(t)) < 0.5) ? 1 : -1;
-                    if (dir_use != dir) {
-                        const int eo2 = (dir_use > 0) ? SL_RIGHT_Q : SL_LEFT_Q;
-                        q = ldv(eo2 + 0); p = ldv(eo2 + 1); g = ldv(eo2 + 2);
-                    }
+                    const int dir_use = bf_pipe_dir(bf_xoshiro_next(t));
+                    turn = dir_use != dir;
+                    eo2 = (dir_use > 0) ? SL_RIGHT_Q : SL_LEFT_Q;
                 }
             }
-            if (evaluating) eps_t = eps * (double)dir_use;
         }
         if (evaluating) {
+            if (turn) {
+                // the next doubling grows from the other end
+                eps_t = bf_pipe_neg(eps_t);  // (eps * -dir to the bit; the pending bookkeeping sets dir to this draw or ends the tree)
+                heps_t = bf_pipe_neg(heps_t);
+                q = ldv(eo2 + 0); p = ldv(eo2 + 1); g = ldv(eo2 + 2);
+            }
             {
-                const double dt = 0.5 * eps_t;
+                const double dt = heps_t;
                 p = p + dt * g;                    // integration.py:80
                 q = q + eps_t * (var * p);         // :82-85
             }
@@ -420,7 +443,10 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
         // (Stages that have nothing to do fall through; the MFMAs then simply queue up.  The FP64 VALU work does not
         // overlap with the MFMAs themselves: they share the pipe.)
         const bool job = ev_mask != 0 && w < NJOB_P;
-        typename PipeAcc<QUAD>::type acc = {};
+        // (no zero-fill: a wave with a job overwrites the accumulator with its first MFMA, a wave without one never stores it;
+        // the empty statement gives the compiler a defined value that costs no instruction)
+        typename PipeAcc<QUAD>::type acc;
+        asm volatile("" : "=v"(acc));
         const double *Xf = XB + ((w / (W * KS_P)) * NS + (w % KS_P) * KPJ_P) * XS + (QUAD ? (lane & ~15) + (lane & 3) : lane);
         double x_pre[MPS], x_pr2[QUAD == 2 ? MPS : 1];
 #pragma unroll
@@ -440,14 +466,26 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
                     if constexpr (QUAD == 2) { _Pragma("unroll") for (int u = 0; u < MPS; ++u) x_pr2[u] = Xf[((((K) + 1) * MPS < KPJ_P ? ((K) + 1) * MPS : 0) + u) * XS + 4]; } \
                 }                                                                                           \
                 _Pragma("unroll") for (int u = 0; u < MPS; ++u) {                                           \
-                    asm volatile("" : "+v"(acc) : : "memory");                                              \
-                    if constexpr (QUAD == 2) {                                                              \
-                        if (job) {                                                                          \
-                            acc[0] = bf_pipe_mfma(afr[((K) * MPS < KPJ_P ? (K) * MPS : 0) + u], x_cur[u], acc[0]); \
-                            acc[1] = bf_pipe_mfma(afr[((K) * MPS < KPJ_P ? (K) * MPS : 0) + u], x_cu2[u], acc[1]); \
+                    if ((K) == 0 && u == 0) {                                                               \
+                        /* the chain's first MFMA takes a literal zero for C: no accumulator to clear */    \
+                        if constexpr (QUAD == 2) {                                                          \
+                            if (job) {                                                                      \
+                                acc[0] = bf_pipe_mfma(afr[0], x_cur[0], 0.);                                \
+                                acc[1] = bf_pipe_mfma(afr[0], x_cu2[0], 0.);                                \
+                            }                                                                               \
+                        } else {                                                                            \
+                            if (job) acc = bf_pipe_mfma(afr[0], x_cur[0], typename PipeAcc<QUAD>::type{});  \
                         }                                                                                   \
                     } else {                                                                                \
-                        if (job) acc = bf_pipe_mfma(afr[((K) * MPS < KPJ_P ? (K) * MPS : 0) + u], x_cur[u], acc); \
+                        asm volatile("" : "+v"(acc) : : "memory");                                          \
+                        if constexpr (QUAD == 2) {                                                          \
+                            if (job) {                                                                      \
+                                acc[0] = bf_pipe_mfma(afr[((K) * MPS < KPJ_P ? (K) * MPS : 0) + u], x_cur[u], acc[0]); \
+                                acc[1] = bf_pipe_mfma(afr[((K) * MPS < KPJ_P ? (K) * MPS : 0) + u], x_cu2[u], acc[1]); \
+                            }                                                                               \
+                        } else {                                                                            \
+                            if (job) acc = bf_pipe_mfma(afr[((K) * MPS < KPJ_P ? (K) * MPS : 0) + u], x_cur[u], acc); \
+                        }                                                                                   \
                     }                                                                                       \
                     asm volatile("" : "+v"(acc) : : "memory");                                              \
                 }                                                                                           \
@@ -504,7 +542,7 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
             T_acc = L0_acc + T_acc;  // :173
             const double Wsum = L0_W + T_W;
             if (Wsum != Wsum) err = 2;
-            const double u = bf_u01(bf_xoshiro_next(rs));  // :163-167, drawn even when turning
+            const double u = bf_pipe_u01(bf_xoshiro_next(rs));  // :163-167, drawn even when turning
             lev = 1;
             if ((r2[0] <= 0.) || (r2[1] <= 0.)) {
                 unit = U_ABORT;
@@ -536,7 +574,7 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
             T_acc = rfl(lsp[LS_ACC]) + T_acc;  // :173
             const double Wsum = rfl(lsp[LS_LS]) + T_W;
             if (Wsum != Wsum) err = 2;
-            const double u = bf_u01(bf_xoshiro_next(rs));  // consumed even when this merge's check says turning
+            const double u = bf_pipe_u01(bf_xoshiro_next(rs));  // consumed even when this merge's check says turning
             const bool keep_t2 = (u * Wsum < T_W) || (u == 0.);
             lev += 1;
             if (turning) {
@@ -599,7 +637,7 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
             {   // :81-83  logbern(ls_new - ls_old)  <=>  U * W_old < W_new
                 const double tree_W = cs_get(CS_TREE_W);
                 if (T_W != T_W || tree_W != tree_W) err = 2;
-                const double u = bf_u01(bf_xoshiro_next(rs));
+                const double u = bf_pipe_u01(bf_xoshiro_next(rs));
                 if ((u * tree_W < T_W) || (u == 0.)) {
                     stv(SL_PROP_Q, TPq);
                     stv(SL_PROPG, TPg);
@@ -627,7 +665,7 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
             if (turning || depth >= a.cfg.max_treedepth) {
                 unit = U_END1;
             } else {
-                dir = (bf_u01(bf_xoshiro_next(rs)) < 0.5) ? 1 : -1;  // nuts.py:210 (phase A read this draw ahead)
+                dir = bf_pipe_dir(bf_xoshiro_next(rs));  // nuts.py:210 (phase A read this draw ahead)
                 i_leaf = 0;
                 unit = U_DONE;
             }
@@ -686,22 +724,20 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
             }
             const double logp_new = f;
             // second half of the leapfrog and the kinetic energy
-            const double dt = 0.5 * eps_t;
+            const double dt = heps_t;
             p = p + dt * gn;        // integration.py:90
             g = gn;
             double kin = p * (var * p);   // metrics.py:88-91
             kin = kin_ready ? r_kin : wave_sum(kin);
             const double E_new = 0.5 * kin - logp_new;  // integration.py:92-93
-            if (mode == M_INIT) {
-                init_tree(E_new, logp_new);
-            } else {
-                pend = true;
-                E_pend = E_new;
-                lp_pend = logp_new;
-                TRp = p;
-                TPq = q;
-                TPg = g;
-            }
+            // (the hand-over's five values are assigned on both paths: nothing reads them before a leaf is pending)
+            E_pend = E_new;
+            lp_pend = logp_new;
+            TRp = p;
+            TPq = q;
+            TPg = g;
+            pend = mode != M_INIT;
+            if (mode == M_INIT) init_tree(E_new, logp_new);
         };
         // Outside the bound (modules/poly.py:480-503) the surrogate is wanted at the projected point x_0 = mu + t (x - mu),
         // t = alpha / beta.  It is linear + quadratic, so S x_0 = S mu + t (S x - S mu) follows from the S x of THIS trip and
@@ -737,7 +773,7 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
                 {  // in-bound gradient is already final: the kinetic energy rides along
                     double ge = gn * jac;
                     if constexpr (TR) ge += gj;
-                    const double pe = p + (0.5 * eps_t) * ge;
+                    const double pe = p + heps_t * ge;
                     r3[0] = pe * (var * pe);
                 }
                 wave_sum_n<3>(r3);
