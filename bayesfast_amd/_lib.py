@@ -128,6 +128,7 @@ SYMBOLS = {
     'bfhip_pipeline_logp_hess': (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     'bfhip_pipeline_laplace_opt': (C.c_int, [_vp, C.POINTER(LaplaceOpts), C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     'bfhip_wave_sum_probe': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    'bfhip_wave_packs_probe': (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
 }
 HESS_FULL, HESS_GAUSS_NEWTON = 0, 1   # BFHIP_HESS_FULL / _GAUSS_NEWTON: hess_kind of the bfhip_pipeline_* Hessian calls
 WSUM_MAX = 7            # BFHIP_WSUM_MAX: values bfhip_wave_sum_probe reduces together

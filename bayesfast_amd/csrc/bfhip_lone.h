@@ -206,8 +206,9 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
         const double c_lo = (TR && lane_ok) ? m.pd[PD_LO * DP + lane] : 0., c_rg = (TR && lane_ok) ? m.pd[PD_RG * DP + lane] : 1.;
         double xs = 0., jac = 1., gj = 0., logdet_l = 0.;
         double q = 0., p = 0., g = 0., var = 1.;
-        double eps = 0., eps_t = 0.;
+        double eps = 0., eps_t = 0., heps_t = 0.;   // the signed step of the doubling under way and its half (bf_nuts_pipe_kernel)
         int dir = 1;
+        bool opening = false;   // the evaluation in flight is the one that opens a launch: the step takes its length with the next verdict
         double *tbl = TB + lane;
         const int xti = (lane & 3) * NS + (lane >> 2);   // x_dim -> row dim & 3, k-step dim >> 2 of the transposed operand
         LoneJobs<W, DEC, LWV::NT> jobs;   // (d <= 32: the integrator waits for the products anyway and takes a share of the jobs)
@@ -231,9 +232,15 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
                 var = lane_ok ? NI[3 * DP + lane] : 1.;
                 eps = v_eps;
                 dir = v_dir;
-                eps_t = v_init ? 0. : eps * (double)dir;
+                opening = v_init != 0;
+                eps_t = opening ? 0. : (dir > 0 ? eps : bf_pipe_neg(eps));   // eps * (double)dir
+                heps_t = rfl(0.5 * eps_t);
             } else {
-                int dir_use = dir;
+                if (opening) {
+                    opening = false;
+                    eps_t = dir > 0 ? eps : bf_pipe_neg(eps);
+                    heps_t = rfl(0.5 * eps_t);
+                }
                 if (v_close) {
                     // the leaf in flight closes its doubling: park the new end (its p is the bookkeeper's to park) and start the
                     // next doubling in the direction the stream will give it (bf_nuts_pipe_kernel, phase A)
@@ -242,8 +249,11 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
                     if (!v_eval) {
                         evaluating = false;
                     } else {
-                        dir_use = v_dir;
+                        const int dir_use = v_dir;
                         if (dir_use != dir) {
+                            // the next doubling grows from the other end: eps * (double)dir_use to the bit
+                            eps_t = bf_pipe_neg(eps_t);
+                            heps_t = bf_pipe_neg(heps_t);
                             const int eo2 = (dir_use > 0) ? SL_RIGHT_Q : SL_LEFT_Q;
                             q = lane_ok ? tbl[(eo2 + 0) * DP] : 0.;
                             p = lane_ok ? tbl[(eo2 + 1) * DP] : 0.;
@@ -252,12 +262,11 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
                         dir = dir_use;
                     }
                 }
-                if (evaluating) eps_t = eps * (double)dir_use;
             }
             // ---- phase A: first half of the leapfrog step, B operands ----
             if (evaluating) {
                 {
-                    const double dt = 0.5 * eps_t;
+                    const double dt = heps_t;
                     p = p + dt * g;                    // integration.py:80
                     q = q + eps_t * (var * p);         // :82-85
                 }
@@ -298,25 +307,30 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
                 constexpr bool fast_kin = !DEC;
                 const double sv = sx - c_smu, gmu = c_smu + c_lin;
                 double r_kin = 0., r_val, r_b2, r_bd2 = 0., r_a[2] = {0., 0.};
+                // (the two sums of the extrapolation are read from the packs only outside the bound)
+                constexpr int NC = DEC == 1 ? 5 : (DEC == 2 ? 4 : 3);
+                double rc[NC];
                 if constexpr (DEC == 1) {
-                    double r5[5] = {(xs - c_dmu) * dgr, __builtin_fma(0.5 * xs, sx, c_lin * xs), xm * hv, xm * gmu, xm * sv};
-                    wave_sum_n<5>(r5);
-                    r_bd2 = r5[0]; r_val = r5[1]; r_b2 = r5[2]; r_a[0] = r5[3]; r_a[1] = r5[4];
+                    rc[0] = (xs - c_dmu) * dgr; rc[1] = __builtin_fma(0.5 * xs, sx, c_lin * xs); rc[2] = xm * hv; rc[3] = xm * gmu; rc[4] = xm * sv;
                 } else if constexpr (DEC == 2) {   // (bf_nuts_pipe_kernel: the decay term's radius is the bound's)
-                    double r4[4] = {__builtin_fma(0.5 * xs, sx, c_lin * xs), xm * hv, xm * gmu, xm * sv};
-                    wave_sum_n<4>(r4);
-                    r_val = r4[0]; r_b2 = r4[1]; r_a[0] = r4[2]; r_a[1] = r4[3];
-                    r_bd2 = r_b2;
+                    rc[0] = __builtin_fma(0.5 * xs, sx, c_lin * xs); rc[1] = xm * hv; rc[2] = xm * gmu; rc[3] = xm * sv;
                 } else {
-                    double r3[3] = {0., __builtin_fma(0.5 * xs, sx, c_lin * xs), xm * hv};
                     {
                         double ge = gn * jac;
                         if constexpr (TR) ge += gj;
-                        const double pe = p + (0.5 * eps_t) * ge;
-                        r3[0] = pe * (var * pe);
+                        const double pe = p + heps_t * ge;
+                        rc[0] = pe * (var * pe);
                     }
-                    wave_sum_n<3>(r3);
-                    r_kin = r3[0]; r_val = r3[1]; r_b2 = r3[2];
+                    rc[1] = __builtin_fma(0.5 * xs, sx, c_lin * xs); rc[2] = xm * hv;
+                }
+                const WavePacks<NC> pc = wave_sum_packs<NC>(rc);
+                if constexpr (DEC == 1) {
+                    r_bd2 = pc.get(0); r_val = pc.get(1); r_b2 = pc.get(2);
+                } else if constexpr (DEC == 2) {
+                    r_val = pc.get(0); r_b2 = pc.get(1);
+                    r_bd2 = r_b2;
+                } else {
+                    r_kin = pc.get(0); r_val = pc.get(1); r_b2 = pc.get(2);
                 }
                 LTRACE(0, 5);
                 double logdet = 0.;
@@ -327,7 +341,11 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
                 if (!(r_b2 < a2 * (1. - 1e-12))) beta = LN_SQRT(r_b2);
                 bool kin_ready = fast_kin;
                 if (beta > m.alpha) {
-                    if constexpr (!DEC) {
+                    if constexpr (DEC == 1) {
+                        r_a[0] = pc.get(3); r_a[1] = pc.get(4);
+                    } else if constexpr (DEC == 2) {
+                        r_a[0] = pc.get(2); r_a[1] = pc.get(3);
+                    } else {
                         r_a[0] = xm * gmu; r_a[1] = xm * sv;
                         wave_sum_n<2>(r_a);
                     }
@@ -347,7 +365,7 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
                     gn += gj;
                 }
                 const double logp_new = f;
-                const double dt = 0.5 * eps_t;
+                const double dt = heps_t;
                 p = p + dt * gn;        // integration.py:90
                 g = gn;
                 double kin = p * (var * p);   // metrics.py:88-91
@@ -449,7 +467,7 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
     };
     auto draw_dir = [&]() {
         for (int k = 0; k < 4; ++k) rs_save[k] = rs[k];
-        dir = (bf_u01(bf_xoshiro_next(rs)) < 0.5) ? 1 : -1;  // nuts.py:210, log(U) < log(1/2)
+        dir = bf_pipe_dir(bf_xoshiro_next(rs));  // nuts.py:210, log(U) < log(1/2)
     };
 
     for (int k = 0; k < 4; ++k) rs[k] = rfl((uint64_t)a.rng[(size_t)chain * 4 + k]);
@@ -530,7 +548,7 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
             const double e_aw = LN_EXPV(aw);
             const double ps0 = L0p + TRp;
             double r2[2] = {ps0 * (var * L0p), ps0 * (var * TRp)};
-            wave_sum_n<2>(r2);
+            const bool turning0 = wave_sum_packs<2>(r2).any_le0();   // (the sums stay in their vector registers: bfhip_wave.h)
             if (unit == U_EVAL) {
                 // multinomial weight exp(-dE) relative to a running offset w_off (exact streaming log-sum-exp)
                 T_W = rfl(e_aw);
@@ -558,7 +576,7 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
                 if (Wsum != Wsum) err = 2;
                 const double u = bf_u01(bf_xoshiro_next(rs));  // :163-167, drawn even when turning
                 lev = 1;
-                if ((r2[0] <= 0.) || (r2[1] <= 0.)) {
+                if (turning0) {
                     unit = U_ABORT;
                 } else {
                     if (!((u * Wsum < T_W) || (u == 0.))) {
@@ -584,8 +602,7 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
                 const double ps1 = S1 + TLp;   // :155-157
                 const double ps2 = B + TPs;    // :158-160
                 double r6[6] = {psum * vA, psum * vD, ps1 * vA, ps1 * vC, ps2 * vB, ps2 * vD};
-                wave_sum_n<6>(r6);
-                const bool turning = (r6[0] <= 0.) || (r6[1] <= 0.) || (r6[2] <= 0.) || (r6[3] <= 0.) || (r6[4] <= 0.) || (r6[5] <= 0.);
+                const bool turning = wave_sum_packs<6>(r6).any_le0();
                 const double *lsp = LS + lev * LS_N;
                 T_acc = rfl(lsp[LS_ACC]) + T_acc;  // :173
                 const double Wsum = rfl(lsp[LS_LS]) + T_W;
@@ -671,14 +688,13 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
                     const double ps1 = TPs + oldL, ps2 = TLp + ps;
                     r6[0] = ps * vN; r6[1] = ps * vR; r6[2] = ps1 * vN; r6[3] = ps1 * vL; r6[4] = ps2 * vT; r6[5] = ps2 * vR;
                 }
-                wave_sum_n<6>(r6);
+                const bool turning = wave_sum_packs<6>(r6).any_le0();
                 stv(SL_PSUM, ps);
                 stv((dir > 0) ? SL_RIGHT_P : SL_LEFT_P, TRp);
-                const bool turning = (r6[0] <= 0.) || (r6[1] <= 0.) || (r6[2] <= 0.) || (r6[3] <= 0.) || (r6[4] <= 0.) || (r6[5] <= 0.);
                 if (turning || depth >= a.cfg.max_treedepth) {
                     unit = U_END1;
                 } else {
-                    dir = (bf_u01(bf_xoshiro_next(rs)) < 0.5) ? 1 : -1;  // nuts.py:210 (announced one leaf ago)
+                    dir = bf_pipe_dir(bf_xoshiro_next(rs));  // nuts.py:210 (announced one leaf ago)
                     i_leaf = 0;
                     unit = U_DONE;
                 }
@@ -811,7 +827,7 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
                 } else {
                     uint64_t t[4] = {rs[0], rs[1], rs[2], rs[3]};
                     for (int k = 0; k <= depth; ++k) (void)bf_xoshiro_next(t);  // `depth` merges and the swap
-                    dir_use = (bf_u01(bf_xoshiro_next(t)) < 0.5) ? 1 : -1;
+                    dir_use = bf_pipe_dir(bf_xoshiro_next(t));
                 }
             }
             if (lane == 0) {

@@ -442,7 +442,11 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
         // code below, so that a wave waiting for its accumulator leaves the issue slots to the stages of the others.
         // (Stages that have nothing to do fall through; the MFMAs then simply queue up.  The FP64 VALU work does not
         // overlap with the MFMAs themselves: they share the pipe.)
-        const bool job = ev_mask != 0 && w < NJOB_P;
+        // (with a job on every wave of a full-tile workgroup the condition is a constant: a trip in which no chain evaluates
+        // multiplies what XB holds and nothing reads the result -- phase C runs under `evaluating` --, and the sites lose their
+        // branches and, with them, the copy of the prefetched operand.  Not behind the transform: there the freed scheduling
+        // cost six more reloads in the trip loop: docs/EXPERIMENTS.md)
+        const bool job = (NJOB_P == 16 && QUAD == 0 && !TR) ? true : (ev_mask != 0 && w < NJOB_P);
         // (no zero-fill: a wave with a job overwrites the accumulator with its first MFMA, a wave without one never stores it;
         // the empty statement gives the compiler a defined value that costs no instruction)
         typename PipeAcc<QUAD>::type acc;
@@ -538,13 +542,13 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
             // ---- level-0 merge with the previous leaf, whose (p, q) wait in L0p / L0q (nuts.py:146-178) ----
             const double ps0 = L0p + TRp;
             double r2[2] = {ps0 * (var * L0p), ps0 * (var * TRp)};  // nuts.py:150-151
-            wave_sum_n<2>(r2);
+            const bool turning = wave_sum_packs<2>(r2).any_le0();   // (the sums stay in their vector registers: bfhip_wave.h)
             T_acc = L0_acc + T_acc;  // :173
             const double Wsum = L0_W + T_W;
             if (Wsum != Wsum) err = 2;
             const double u = bf_pipe_u01(bf_xoshiro_next(rs));  // :163-167, drawn even when turning
             lev = 1;
-            if ((r2[0] <= 0.) || (r2[1] <= 0.)) {
+            if (turning) {
                 unit = U_ABORT;
             } else {
                 if (!((u * Wsum < T_W) || (u == 0.))) {
@@ -560,16 +564,26 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
         }
         BF_MF(3);
         // ---- merge upwards while the finished subtree is a right child (nuts.py:146-178) ----
-        while (unit == U_MERGE && lev < depth && ((i_leaf >> lev) & 1)) {
+        // (level 1 waits in LDS, at constant offsets, the levels above it in global scratch: the level is known before the loads
+        // are issued, so the pass for level 1 is peeled off the loop and neither form chooses its memory at run time)
+        auto merge_level = [&](auto in_lds) {
+            constexpr bool LDS1 = decltype(in_lds)::value;
             const int slot = SL_STACK + 4 * lev;
-            const double A = ldv(slot + 0), B = ldv(slot + 1), S1 = ldv(slot + 2);
+            auto ldl = [&](int k) -> double {   // vector k of this level
+                double v = 0.;
+                if (lane_ok) {
+                    if constexpr (LDS1) v = tbw[(SL_STACK + k) * DP];
+                    else v = sbase[(size_t)(slot + k) * DP];
+                }
+                return v;
+            };
+            const double A = ldl(0), B = ldl(1), S1 = ldl(2);
             const double psum = S1 + TPs;
             const double vA = var * A, vB = var * B, vC = var * TLp, vD = var * TRp;
             const double ps1 = S1 + TLp;   // :155-157
             const double ps2 = B + TPs;    // :158-160
             double r6[6] = {psum * vA, psum * vD, ps1 * vA, ps1 * vC, ps2 * vB, ps2 * vD};
-            wave_sum_n<6>(r6);
-            const bool turning = (r6[0] <= 0.) || (r6[1] <= 0.) || (r6[2] <= 0.) || (r6[3] <= 0.) || (r6[4] <= 0.) || (r6[5] <= 0.);
+            const bool turning = wave_sum_packs<6>(r6).any_le0();
             const double *lsp = lsw + lev * LS_N;
             T_acc = rfl(lsp[LS_ACC]) + T_acc;  // :173
             const double Wsum = rfl(lsp[LS_LS]) + T_W;
@@ -581,8 +595,8 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
                 unit = U_ABORT;  // ancestors above this level still add their accept sums
             } else {
                 if (!keep_t2) {
-                    TPq = ldv(slot + 3);  // the sibling's proposal
-                    TPg = ldv(SL_PG + lev - 1);
+                    TPq = ldl(3);  // the sibling's proposal
+                    TPg = lane_ok ? sbase[(size_t)(SL_PG + lev - 1) * DP] : 0.;   // (the gradients of every level: global scratch)
                     cs_set(CS_T_E, rfl(lsp[LS_E]));
                     cs_set(CS_T_LOGP, rfl(lsp[LS_LOGP]));
                 }
@@ -590,7 +604,9 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
                 TLp = A;
                 TPs = psum;
             }
-        }
+        };
+        if (unit == U_MERGE && lev == 1 && lev < depth && ((i_leaf >> 1) & 1)) merge_level(std::true_type{});
+        while (unit == U_MERGE && lev < depth && ((i_leaf >> lev) & 1)) merge_level(std::false_type{});   // (lev >= 2 here)
         BF_MF(4);
         TRACE(10);
         if (unit == U_MERGE) {
@@ -658,10 +674,9 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
                 const double ps1 = TPs + oldL, ps2 = TLp + ps;
                 r6[0] = ps * vN; r6[1] = ps * vR; r6[2] = ps1 * vN; r6[3] = ps1 * vL; r6[4] = ps2 * vT; r6[5] = ps2 * vR;
             }
-            wave_sum_n<6>(r6);
+            const bool turning = wave_sum_packs<6>(r6).any_le0();
             stv(SL_PSUM, ps);
             stv((dir > 0) ? SL_RIGHT_P : SL_LEFT_P, TRp);
-            const bool turning = (r6[0] <= 0.) || (r6[1] <= 0.) || (r6[2] <= 0.) || (r6[3] <= 0.) || (r6[4] <= 0.) || (r6[5] <= 0.);
             if (turning || depth >= a.cfg.max_treedepth) {
                 unit = U_END1;
             } else {
@@ -755,29 +770,35 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
             const double sv = sx - c_smu, gmu = c_smu + c_lin;   // S (x - mu), the gradient at mu (bfhip_oob.h)
             double r_kin = 0., r_val, r_b2, r_bd2 = 0., r_a[2] = {0., 0.};
             TRACE(7);
+            // (the first reduction: what the common path wants of it is read here, the two sums of the extrapolation only outside
+            // the bound, from the packs)
+            constexpr int NC = DEC == 1 ? 5 : (DEC == 2 ? 4 : 3);
+            double rc[NC];
             if constexpr (DEC == 1) {
                 // (the densities that carry the decay term live outside the bound: its sum and the two sums of the extrapolation
                 // ride in the first reduction -- the same numbers as reductions of their own)
-                double r5[5] = {(xs - c_dmu) * dgr, __builtin_fma(0.5 * xs, sx, c_lin * xs), xm * hv, xm * gmu, xm * sv};
-                wave_sum_n<5>(r5);
-                r_bd2 = r5[0]; r_val = r5[1]; r_b2 = r5[2]; r_a[0] = r5[3]; r_a[1] = r5[4];
+                rc[0] = (xs - c_dmu) * dgr; rc[1] = __builtin_fma(0.5 * xs, sx, c_lin * xs); rc[2] = xm * hv; rc[3] = xm * gmu; rc[4] = xm * sv;
             } else if constexpr (DEC == 2) {
                 // (the decay term's radius IS the bound's: (x - mu_d) . H_d (x - mu_d) = (x - mu) . H (x - mu), the same products summed
                 // the same way)
-                double r4[4] = {__builtin_fma(0.5 * xs, sx, c_lin * xs), xm * hv, xm * gmu, xm * sv};
-                wave_sum_n<4>(r4);
-                r_val = r4[0]; r_b2 = r4[1]; r_a[0] = r4[2]; r_a[1] = r4[3];
-                r_bd2 = r_b2;
+                rc[0] = __builtin_fma(0.5 * xs, sx, c_lin * xs); rc[1] = xm * hv; rc[2] = xm * gmu; rc[3] = xm * sv;
             } else {
-                double r3[3] = {0., __builtin_fma(0.5 * xs, sx, c_lin * xs), xm * hv};
                 {  // in-bound gradient is already final: the kinetic energy rides along
                     double ge = gn * jac;
                     if constexpr (TR) ge += gj;
                     const double pe = p + heps_t * ge;
-                    r3[0] = pe * (var * pe);
+                    rc[0] = pe * (var * pe);
                 }
-                wave_sum_n<3>(r3);
-                r_kin = r3[0]; r_val = r3[1]; r_b2 = r3[2];
+                rc[1] = __builtin_fma(0.5 * xs, sx, c_lin * xs); rc[2] = xm * hv;
+            }
+            const WavePacks<NC> pc = wave_sum_packs<NC>(rc);
+            if constexpr (DEC == 1) {
+                r_bd2 = pc.get(0); r_val = pc.get(1); r_b2 = pc.get(2);
+            } else if constexpr (DEC == 2) {
+                r_val = pc.get(0); r_b2 = pc.get(1);
+                r_bd2 = r_b2;
+            } else {
+                r_kin = pc.get(0); r_val = pc.get(1); r_b2 = pc.get(2);
             }
             TRACE(8);
             double logdet = 0.;
@@ -788,7 +809,11 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
             if (!(r_b2 < a2 * (1. - 1e-12))) beta = usqrt(r_b2);
             bool kin_ready = fast_kin;
             if (beta > m.alpha) {
-                if constexpr (!DEC) {
+                if constexpr (DEC == 1) {
+                    r_a[0] = pc.get(3); r_a[1] = pc.get(4);
+                } else if constexpr (DEC == 2) {
+                    r_a[0] = pc.get(2); r_a[1] = pc.get(3);
+                } else {
                     r_a[0] = xm * gmu; r_a[1] = xm * sv;
                     wave_sum_n<2>(r_a);
                 }

@@ -66,22 +66,67 @@ __device__ inline void wave_sum_n_unpacked(double (&v)[N]) {
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] = rfl(v[i]);
 }
+// The reduction with its results left where the arithmetic puts them (default form: the packs after the two row rotations, every
+// lane of column j of pack c holding value 4 c + j; a padding column of a short pack repeats one of the pack's own values).
+// get(i) reads one value into scalar registers -- the bits of wave_sum_n --, any_le0() asks whether some value is <= 0. (ordered:
+// false for NaN, true for +-0. and -inf) with one compare per pack on the packed register, the lane masks OR-ed on the scalar
+// unit: a U-turn test, which wants nothing but that answer, reads no sum.  With BF_WSUM_UNPACKED / BF_WSUM_BUTTERFLY the values
+// are wave-uniform already and the test is the scalar expression; BF_UTURN_READ_ALL keeps that read-everything form of the test
+// in the default build too (tools/svariant.sh readall -DBF_UTURN_READ_ALL, for a comparison on the device).
+#if defined(BF_WSUM_UNPACKED) || defined(BF_WSUM_BUTTERFLY)
+#define BF_WSUM_UNIFORM 1
+#endif
+template <int N>
+struct WavePacks {
+#ifdef BF_WSUM_UNIFORM
+    static constexpr int NP = N;
+#else
+    static constexpr int NP = N == 1 ? 1 : (N + 3) / 4;
+#endif
+    double pk[NP];
+    __device__ inline double get(int i) const {
+#ifdef BF_WSUM_UNIFORM
+        return pk[i];
+#else
+        if constexpr (N == 1) return rfl(pk[0]);
+        else return (i & 3) ? readlane_f64(pk[i >> 2], i & 3) : rfl(pk[i >> 2]);
+#endif
+    }
+    __device__ inline bool any_le0() const {
+#if defined(BF_WSUM_UNIFORM) || defined(BF_UTURN_READ_ALL)
+        bool t = false;
+#pragma unroll
+        for (int i = 0; i < N; ++i) t = t || (get(i) <= 0.);
+        return t;
+#else
+        uint64_t mask = 0;
+#pragma unroll
+        for (int c = 0; c < NP; ++c) mask |= __builtin_amdgcn_ballot_w64(pk[c] <= 0.);
+        return mask != 0;
+#endif
+    }
+};
 // The first MFMA's result is the same in the four columns j of a block, and the second MFMA and the rotations (by 8 and 4
 // lanes) never mix columns: the unpacked form does the same arithmetic four times over.  Here column j carries value
 // 4 c + j of pack c -- the operand of the second step takes lane l from value (l & 3) -- and value 4 c + j is read from
 // lane j.  Every column sees the operations of the unpacked form in the same order: bit-identical results, and a NaN or
 // an infinity stays in its own value's column.  (Like the rotations of the unpacked form, this wants all 64 lanes active:
 // the callers reduce under wave-uniform control flow only.)
+// (the packed form by name -- the probe runs it whatever the library was built with --: the packs after the two row rotations)
 template <int N>
-__device__ inline void wave_sum_n_packed(double (&v)[N]) {
+__device__ inline void wave_packs_packed(double (&v)[N], double (&pk)[N == 1 ? 1 : (N + 3) / 4]) {
     if constexpr (N == 1) {
-        wave_sum_n_unpacked<1>(v);
+        // (one value: nothing to pack; the unpacked form without its read)
+        double t = __builtin_amdgcn_mfma_f64_4x4x4f64(v[0], 1., 0., 0, 0, 0);
+        t = __builtin_amdgcn_mfma_f64_4x4x4f64(1., t, 0., 0, 0, 0);
+        t += dpp_f64<0x128>(t);  // row_ror:8
+        t += dpp_f64<0x124>(t);  // row_ror:4
+        pk[0] = t;
     } else {
         constexpr int NP = (N + 3) / 4;
         const bool odd = threadIdx.x & 1, upper = threadIdx.x & 2;   // bits 0 and 1 of the lane
 #pragma unroll
         for (int i = 0; i < N; ++i) v[i] = __builtin_amdgcn_mfma_f64_4x4x4f64(v[i], 1., 0., 0, 0, 0);
-        double pk[NP];
 #pragma unroll
         for (int c = 0; c < NP; ++c) {
             const int b = 4 * c, m = (N - b < 4) ? N - b : 4;   // the values of this pack; a column without one repeats another
@@ -97,17 +142,21 @@ __device__ inline void wave_sum_n_packed(double (&v)[N]) {
         for (int c = 0; c < NP; ++c) pk[c] += dpp_f64<0x128>(pk[c]);  // row_ror:8
 #pragma unroll
         for (int c = 0; c < NP; ++c) pk[c] += dpp_f64<0x124>(pk[c]);  // row_ror:4
+    }
+}
+template <int N>
+__device__ inline void wave_sum_n_packed(double (&v)[N]) {
+    double pk[N == 1 ? 1 : (N + 3) / 4];
+    wave_packs_packed<N>(v, pk);
+    if constexpr (N == 1) {
+        v[0] = rfl(pk[0]);
+    } else {
 #pragma unroll
         for (int i = 0; i < N; ++i) v[i] = (i & 3) ? readlane_f64(pk[i >> 2], i & 3) : rfl(pk[i >> 2]);
     }
 }
 template <int N>
-__device__ inline void wave_sum_n(double (&v)[N]) {
-#if defined(BF_WSUM_UNPACKED)
-    wave_sum_n_unpacked<N>(v);
-#elif !defined(BF_WSUM_BUTTERFLY)
-    wave_sum_n_packed<N>(v);
-#else
+__device__ inline void wave_sum_n_butterfly(double (&v)[N]) {
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] += dpp_f64<0xB1>(v[i]);   // quad_perm [1,0,3,2]
 #pragma unroll
@@ -122,7 +171,29 @@ __device__ inline void wave_sum_n(double (&v)[N]) {
     for (int i = 0; i < N; ++i) v[i] = swap32_add_f64(v[i]);
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] = rfl(v[i]);
+}
+// (v is used up: it holds intermediate values afterwards)
+template <int N>
+__device__ inline WavePacks<N> wave_sum_packs(double (&v)[N]) {
+    WavePacks<N> r;
+#if defined(BF_WSUM_UNPACKED)
+    wave_sum_n_unpacked<N>(v);
+#pragma unroll
+    for (int i = 0; i < N; ++i) r.pk[i] = v[i];
+#elif defined(BF_WSUM_BUTTERFLY)
+    wave_sum_n_butterfly<N>(v);
+#pragma unroll
+    for (int i = 0; i < N; ++i) r.pk[i] = v[i];
+#else
+    wave_packs_packed<N>(v, r.pk);
 #endif
+    return r;
+}
+template <int N>
+__device__ inline void wave_sum_n(double (&v)[N]) {
+    const WavePacks<N> r = wave_sum_packs<N>(v);
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = r.get(i);
 }
 __device__ inline double wave_sum(double v) {
     double t[1] = {v};

@@ -37,7 +37,8 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_DIM 128         /* input_size limit of the device path */
 #define BFHIP_MAX_TREEDEPTH 12
 
-/* 107: bfhip_pipeline_logp_hess and bfhip_pipeline_laplace_opt, the analytic and the Gauss-Newton Hessian of the pipeline density and
+/* 108: bfhip_wave_packs_probe.
+ * 107: bfhip_pipeline_logp_hess and bfhip_pipeline_laplace_opt, the analytic and the Gauss-Newton Hessian of the pipeline density and
  * its device Newton maximiser.  106: bfhip_wave_sum_probe.
  * 105: bfhip_diag_columns, bfhip_diag_extent, bfhip_diag_sort and bfhip_diag_rank, the data passes of split-R-hat, ESS and the posterior summary.
  * 104: bfhip_logp_hess and bfhip_laplace_opt, the analytic Hessian of the surrogate density and the device Newton maximiser.
@@ -588,6 +589,11 @@ int bfhip_pipeline_laplace_opt(bfhip_ctx *ctx, const bfhip_laplace_opts *opts, i
 #define BFHIP_WSUM_PACKED 1
 #define BFHIP_WSUM_UNPACKED 2
 int bfhip_wave_sum_probe(bfhip_ctx *ctx, int n_batch, int n_val, int form, const double *in, double *out);
+/* The same reduction with its results left in the vector registers (csrc/bfhip_wave.h: wave_sum_packs), in the form the library was
+ * built with: out (n_batch, n_val) the values read one by one (get), flag (n_batch) ints, 1 where any_le0() holds -- some value of
+ * the batch is <= 0., an ordered compare: false for NaN, true for +-0. and -inf -- which the U-turn tests of the NUTS kernels take
+ * without reading a sum.  Same argument rules. */
+int bfhip_wave_packs_probe(bfhip_ctx *ctx, int n_batch, int n_val, const double *in, double *out, int *flag);
 
 /* NOT part of this interface: the library's test and tuning switches (force a chain layout, a kernel form or a chains-per-workgroup
  * count; attach measurement buffers; run a launch in one part).  They have ONE entry point each for integers and for buffers,

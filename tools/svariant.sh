@@ -1,7 +1,8 @@
 #!/bin/bash
 # Tuning build of the wave-per-chain sampler kernels: compile bfhip_sampler.hip with extra -D flags and link it with the
 # other objects (the Makefile's SRCS, built by make) into bayesfast_amd/variants/libbfhip_s_<name>.so.  Select it with
-# BFHIP_LIBRARY=<path>.  E.g. the unpacked form of the wave reductions next to the default: tools/svariant.sh unpacked -DBF_WSUM_UNPACKED
+# BFHIP_LIBRARY=<path>.  E.g. the unpacked form of the wave reductions next to the default: tools/svariant.sh unpacked -DBF_WSUM_UNPACKED;
+# the U-turn tests that read every sum (the form before any_le0): tools/svariant.sh readall -DBF_UTURN_READ_ALL
 # usage: tools/svariant.sh <name> [-DFLAG=..]...
 set -e
 name=$1; shift
