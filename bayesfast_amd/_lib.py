@@ -123,6 +123,11 @@ SYMBOLS = {
     'bfhip_diag_extent': (C.c_int, [_vp, C.c_int, C.c_long, _vp, _vp, _vp]),
     'bfhip_diag_sort': (C.c_int, [_vp, C.c_long, _vp, C.c_int, _vp, _vp]),
     'bfhip_diag_rank': (C.c_int, [_vp, C.c_long, _vp, _vp, C.c_int, _vp]),
+    'bfhip_psis': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, C.c_size_t]),
+    'bfhip_wstat_columns': (C.c_int, [_vp, C.c_int, C.c_long, C.c_long, C.c_long, _vp, C.c_int, C.c_long, C.c_int, C.c_int, _vp, _vp]),
+    'bfhip_wstat_moments': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
+    'bfhip_wstat_cumweights': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp]),
+    'bfhip_wstat_quantiles': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp]),
     'bfhip_logp_hess': (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     'bfhip_laplace_opt': (C.c_int, [_vp, C.POINTER(LaplaceOpts), C.c_int, _vp, _vp, _vp, _vp, _vp]),
     'bfhip_pipeline_logp_hess': (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
@@ -135,6 +140,14 @@ WSUM_MAX = 7            # BFHIP_WSUM_MAX: values bfhip_wave_sum_probe reduces to
 WSUM_FORMS = {'built': 0, 'packed': 1, 'unpacked': 2}   # BFHIP_WSUM_BUILT / _PACKED / _UNPACKED
 ACOR_MAX_GROUPS = 256   # walker groups of bfhip_acor_lag_sums: its work buffer is min(n_w, 256) * n_lag * n_d doubles
 DIAG_BATCH = 16         # BFHIP_DIAG_BATCH: parameters per batch of the bfhip_diag_* passes (the width of their series buffers)
+WSTAT_WORK = 65536      # BFHIP_WSTAT_WORK: doubles of bfhip_wstat_moments' work buffer
+WSTAT_TILE = 2048       # sorted positions per workgroup of bfhip_wstat_cumweights: its work buffer is ceil(n / 2048) doubles
+
+
+def psis_work_bytes(n):
+    """BFHIP_PSIS_WORK_BYTES(n)"""
+    return 16 * int(n) + 32768
+
 
 _lib = None
 

@@ -460,6 +460,21 @@ class TraceTuple:
         from ..utils import diagnostics
         return diagnostics.summary(self._diag_input(since_iter, include_warmup, original_space, return_type), probs, prob)
 
+    def weighted_summary(self, log_weights, since_iter=None, include_warmup=False, original_space=True, return_type='samples',
+                         probs=(0.05, 0.5, 0.95)):
+        """The table of mean, sd, quantiles, mcse_mean, ess and ess_kish per parameter of the draws under the importance weights
+        ``log_weights`` (``bayesfast_amd.utils.weighted_summary``; one log weight per selected draw, shaped (n_chain, n_t) or flat
+        in that order, e.g. ``psis(...).log_weights``), read where ``sample()`` left the chains; selection as ``summary``.  Single
+        process only: with more than one rank it raises ``NotImplementedError``."""
+        from .. import parallel
+        from ..utils.psis import weighted_summary
+        if parallel.world()[1] > 1:
+            raise NotImplementedError('the weights are normalised over the draws of ALL chains, and this TraceTuple holds one rank\'s: '
+                                      'gather the chains and use the host port, '
+                                      'utils.weighted_summary(tt.gather().get(flatten=False), log_weights).')
+        return weighted_summary(self._diag_input(since_iter, include_warmup, original_space, return_type), log_weights=log_weights,
+                                probs=probs)
+
     def __getitem__(self, key):
         return self.sample_traces[key]
 

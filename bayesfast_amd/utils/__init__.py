@@ -1,6 +1,8 @@
 from .acor import integrated_time, AutocorrError
 from .resample import SystematicResampler
 from .diagnostics import rhat, ess, summary
+from .psis import psis, PSISResult, weighted_summary
 from .laplace import Laplace, LaplaceResult, make_positive
 
-__all__ = ['SystematicResampler', 'integrated_time', 'AutocorrError', 'Laplace', 'LaplaceResult', 'make_positive', 'rhat', 'ess', 'summary']
+__all__ = ['SystematicResampler', 'integrated_time', 'AutocorrError', 'Laplace', 'LaplaceResult', 'make_positive', 'rhat', 'ess', 'summary',
+           'psis', 'PSISResult', 'weighted_summary']

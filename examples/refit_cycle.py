@@ -59,6 +59,16 @@ def main():
     w, wt = bfa.importance_weights(logp_true(x[sub]), logq[sub])
     ess = wt.sum()**2 / np.sum(wt**2)
     print('importance weights of the final samples: effective sample size %.0f of %d (%.1f %%)' % (ess, wt.size, 100 * ess / wt.size))
+    # is the surrogate good enough for these weights to mean anything, and what is the posterior once they are applied?
+    import torch
+    from bayesfast_amd.utils import psis, weighted_summary
+    xs = torch.as_tensor(x[sub], device='cuda')
+    r = psis(torch.as_tensor(logp_true(x[sub]), device='cuda'), torch.as_tensor(logq[sub], device='cuda'))
+    print('Pareto-smoothed weights: khat %.3f (%s), tail of %d, effective sample size %.0f, log mean weight %.4f' % (
+        r.khat, 'good' if r.khat < 0.5 else ('usable' if r.khat < 0.7 else 'unreliable: refit once more'), r.n_tail, r.ess,
+        r.log_mean_weight))
+    print('weighted posterior of the first 4 parameters:')
+    print(weighted_summary(xs[:, :4], log_weights=r.log_weights))
 
 
 if __name__ == '__main__':

@@ -37,7 +37,8 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_DIM 128         /* input_size limit of the device path */
 #define BFHIP_MAX_TREEDEPTH 12
 
-/* 108: bfhip_wave_packs_probe.
+/* 108: bfhip_wave_packs_probe; bfhip_psis and bfhip_wstat_columns / _moments / _cumweights / _quantiles, the Pareto-smoothed importance
+ * weights and the weighted posterior table (additions only: the number stays).
  * 107: bfhip_pipeline_logp_hess and bfhip_pipeline_laplace_opt, the analytic and the Gauss-Newton Hessian of the pipeline density and
  * its device Newton maximiser.  106: bfhip_wave_sum_probe.
  * 105: bfhip_diag_columns, bfhip_diag_extent, bfhip_diag_sort and bfhip_diag_rank, the data passes of split-R-hat, ESS and the posterior summary.
@@ -519,6 +520,56 @@ int bfhip_diag_columns(bfhip_ctx *ctx, int n_chain, long h, long ldw, long ldr, 
 int bfhip_diag_extent(bfhip_ctx *ctx, int n_series, long h, const double *series, double *lo, double *hi);
 int bfhip_diag_sort(bfhip_ctx *ctx, long n, const double *series, int b, uint64_t *keys_sorted, uint32_t *order);
 int bfhip_diag_rank(bfhip_ctx *ctx, long n, const uint64_t *keys_sorted, const uint32_t *order, int b, double *z);
+
+/* Pareto-smoothed importance sampling (Vehtari, Simpson, Gelman, Yao, Gabry 2024; bayesfast_amd/utils/psis.py has the definitions) of
+ * n log ratios lw = logp - logq (logq NULL: logp holds the ratios), all (n,) float64 on the device, n <= 2^31 - 1.  One call, one fixed
+ * launch sequence (the tail size M = min(n / 5, ceil(3 sqrt n)) and the m = 30 + floor(sqrt M) candidate thetas follow from n):
+ * the ratios, their maximum and a flag for a NaN or +inf; the shift by the maximum; the stable sort of bfhip_sort_keys; the
+ * generalised-Pareto fit of Zhang & Stephens (2009) to the M largest exceedances exp(lw) - exp(cut) over the value at sorted position
+ * n - M - 1 -- a workgroup per theta_j reduces log1p(-theta_j x_i), one workgroup forms the profile likelihoods, their weights, theta,
+ * k, sigma = -k / theta and khat = (k M + 5) / (M + 10); the scatter of log(exp(cut) + sigma expm1(-khat log1p(-p_i)) / khat),
+ * p_i = (i - 1/2) / M, capped at 0, through the sort's permutation; a two-level logsumexp and sum of squares; the normalisation.
+ *   lw_out (n,)  the smoothed log weights, logsumexp 0, in the input's order (also the call's working copy of the ratios)
+ *   out8 (8,)    khat, sigma, M, cut, log mean weight (maximum + logsumexp - log n of the smoothed, shifted values: the estimate of
+ *                log Z_p / Z_q), the Kish effective sample size 1 / sum w^2, the maximum that was subtracted, flags
+ *                (1: a NaN or +inf ratio, or no ratio above -inf -- every output is NaN; 2: no smoothing -- M < 5 or a tail without
+ *                spread -- khat = inf, sigma = NaN)
+ *   work         BFHIP_PSIS_WORK_BYTES(n) bytes of the caller's, 8-byte aligned: sorted keys, permutation, partial results
+ * -inf ratios are zero weights, sort first and count in n.  Every reduction has a fixed order (a thread adds in index order, a
+ * workgroup by a halving tree, one workgroup the at most 1024 partial results): bitwise repeatable.  Stream-ordered; the sort
+ * keeps its temporary storage in the context's workspace, which synchronises only when it has to grow. */
+#define BFHIP_PSIS_WORK_BYTES(n) (16 * (size_t)(n) + 32768)
+int bfhip_psis(bfhip_ctx *ctx, long n, const double *logp, const double *logq, double *lw_out, double *out8, void *work,
+               size_t work_bytes);
+
+/* The weighted table of mean, sd and quantiles (bayesfast_amd/utils/psis.py: weighted_summary), on a batch of at most
+ * BFHIP_DIAG_BATCH parameters and weights w (n,) >= 0 that sum to 1:
+ *   bfhip_wstat_columns     columns k0 .. k0 + nb - 1 of the time-major sample tensor -> out (n_chain n_draw, BFHIP_DIAG_BATCH), row
+ *                           c n_draw + i <- x[c ldw + (since + i) ldr + k], the addressing of bfhip_diag_columns (float64, or float32
+ *                           read as float64; a [:, since:] view goes in without a copy) but without the split: every draw is kept.
+ *                           Columns nb .. BFHIP_DIAG_BATCH - 1 are written as 0.  With w (n,) given (it may be NULL) the rows of zero
+ *                           weight are written as NaN: they are not part of the weighted sample whatever they hold, and sort last.
+ *   bfhip_wstat_moments     series NULL: wsum (4,) <- sum w, sum w^2, the number of non-zero weights, 1 if a weight is negative or not
+ *                           finite -- computed once per weight vector.  series (n, BFHIP_DIAG_BATCH): out (5, BFHIP_DIAG_BATCH) <-
+ *                           per column sum w x, then on a second pass over the data sum w (x - mean)^2 and sum w^2 (x - mean)^2, and
+ *                           the smallest and the largest value, all over the rows of non-zero weight (a NaN among them shows in the
+ *                           sums, not in the extremes).  work: BFHIP_WSTAT_WORK doubles.
+ *   bfhip_wstat_cumweights  cum[p] = sum_{p' <= p} w[order[p']] for the permutation order (n,) of bfhip_diag_sort.  Three launches:
+ *                           the sums of tiles of 2048 sorted positions, their scan by ONE workgroup, the final pass; no workgroup
+ *                           waits on another, any n <= 2^31 - 1.  Exact for whole-number weights.  work: ceil(n / 2048) doubles.
+ *   bfhip_wstat_quantiles   out[i BFHIP_DIAG_BATCH + b] <- the weighted quantile at probs[i] (nq device doubles in [0, 1]) over the
+ *                           first wsum[2] sorted positions: with mid_k = cum[k] - w_(k) / 2 and pos_k = (mid_k - mid_first) /
+ *                           (mid_last - mid_first), k the last position with pos_k <= q by bisection, the value interpolated linearly
+ *                           between positions k and k + 1 (the last value for the last k); values decoded from keys_sorted.
+ * Stream-ordered, no host synchronisation; fixed-order reductions in which a column never meets its neighbours: bitwise
+ * repeatable, whichever batch or column a parameter lands in. */
+#define BFHIP_WSTAT_WORK 65536
+int bfhip_wstat_columns(bfhip_ctx *ctx, int n_chain, long n_draw, long ldw, long ldr, const void *x, int is_f32, long since, int k0,
+                        int nb, const double *w, double *out);
+int bfhip_wstat_moments(bfhip_ctx *ctx, long n, const double *series, const double *w, double *wsum, double *out, double *work);
+int bfhip_wstat_cumweights(bfhip_ctx *ctx, long n, const uint32_t *order, const double *w, double *cum, double *work);
+int bfhip_wstat_quantiles(bfhip_ctx *ctx, long n, const uint64_t *keys_sorted, const uint32_t *order, const double *w, const double *cum,
+                          const double *wsum, int nq, const double *probs, int b, double *out);
 
 /* The OptimizeStep's Laplace approximation (utils/laplace.py:131-183; the reference differences the gradient with numdifftools, at
  * every Newton-CG iteration and once more at the maximum, one point per call).  Both calls take the uploaded SCALAR surrogate density
