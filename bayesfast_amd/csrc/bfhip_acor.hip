@@ -14,7 +14,7 @@
 // walkers in order, then waves, walker slots and walker groups in order), set by the shape alone: the result is bitwise
 // repeatable and the same whichever lag block computes a lag.  No float atomics, 64-bit offsets throughout.
 #include <cmath>
-#include "bfhip_common.h"
+#include "bfhip_block.h"
 
 #define AC_SLOTS 16                       // series per workgroup
 #define AC_R 16                           // lags per lane
@@ -51,9 +51,7 @@ __global__ __launch_bounds__(256) void bf_acor_moments_kernel(int n_w, long n_t,
         for (long s = sl; s < n_t; s += 16) sm += xs[s * n_d];
     red[threadIdx.x] = sm;
     __syncthreads();
-    double m = 0.;
-    for (int i = 0; i < 16; ++i) m += red[i * 16 + q];
-    m /= (double)n_t;
+    const double m = bf_slice_fold(0., 0, red, q, BfSum()) / (double)n_t;   // (every thread, from a literal 0)
     __syncthreads();
     double sq = 0.;
     if (ok)
@@ -64,8 +62,7 @@ __global__ __launch_bounds__(256) void bf_acor_moments_kernel(int n_w, long n_t,
     red[threadIdx.x] = sq;
     __syncthreads();
     if (sl == 0 && ok) {
-        double a0 = 0.;
-        for (int i = 0; i < 16; ++i) a0 += red[i * 16 + q];
+        const double a0 = bf_slice_fold(0., 0, red, q, BfSum());
         mean[id] = m;
         inv[id] = 1. / a0;   // a constant series: 1 / 0 = inf, and its lag sums 0 * inf = NaN, as the host port's 0 / 0
     }

@@ -25,6 +25,10 @@ __device__ inline uint64_t bf_order_key(double v) {
     const uint64_t b = (uint64_t)__double_as_longlong(v);
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
+// the value behind such a key: -0 comes back as +0, every NaN as one NaN
+__device__ inline double bf_order_value(uint64_t k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
 
 #define BF_HIP_CHECK(expr)                                                                 \
     do {                                                                                   \
@@ -108,6 +112,18 @@ static inline int bf_grow(bfhip_ctx *ctx, void **buf, size_t *bytes, size_t need
     *bytes = need;
     return 0;
 }
+
+// ---- shared by the statistics files ------------------------------------------------------------------------
+// bfhip_refit.hip: stable radix sort (rocPRIM) of the order keys of a[i * stride + col], i < n, with the permutation as Index
+// (int64_t: bfhip_sort_keys, uint32_t: bfhip_diag_sort).  Unsorted keys, indices and rocPRIM's temporary storage live in
+// ctx->scratch, each padded to 256 bytes.  The caller has checked its arguments, 1 <= n <= 2^31 - 1.
+template <typename Index>
+int bf_sort_column(bfhip_ctx *ctx, long n, const double *a, long stride, int col, uint64_t *keys_sorted, Index *order);
+// bfhip_diag.hip: the gather of a batch of columns of the (chain, time, dimension) tensor into n_el = rows x 16 doubles, a chain
+// cut into `split` pieces of h steps (2: bfhip_diag_columns, 1: bfhip_wstat_columns).  x is offset by off elements; the caller
+// has checked its arguments.
+int bf_columns_launch(bfhip_ctx *ctx, int split, long n_el, long h, long ldw, long ldr, const void *x, int is_f32, long off, int nb,
+                      int mode, const double *c, const double *w, double *out);
 
 // the common surrogate: linear + quadratic configs with the extrapolation bound; decay term and constraint transform optional
 static inline bool bf_common_surrogate(const DevModel &m) {

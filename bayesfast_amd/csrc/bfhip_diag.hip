@@ -12,29 +12,48 @@
 // the chain moments and lag sums on it (bfhip_acor_moments, bfhip_acor_lag_sums with n_d = DG_B) run in one shape and one
 // summation order whichever batch a parameter falls in.  Everything here is elementwise, a minimum / maximum, a stable sort or a search: no
 // floating-point reduction, bitwise repeatable.  64-bit offsets throughout.
-#include <rocprim/device/device_radix_sort.hpp>
-#include "bfhip_common.h"
+#include "bfhip_block.h"
 #include "bfhip_ndtri.h"
 
 #define DG_B BFHIP_DIAG_BATCH
-static_assert((DG_B & (DG_B - 1)) == 0, "the column index is taken with a mask");
+static_assert(DG_B == 16 && 256 / DG_B == BF_SLICES, "the column index is taken with a mask; bf_slice_fold's layout");
 
-// ---- columns: element e = (split chain j, step i, column b), b fastest -----------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void bf_diag_columns_kernel(long n_el, long h, long ldw, long ldr, const T *__restrict__ x, int nb,
-                                                             int mode, const double *__restrict__ c, double *__restrict__ out) {
+// ---- columns: element e = (piece j, step i, column b), b fastest ------------------------------------------------------------------
+// A chain is cut into SPLIT pieces of h steps: piece j = SPLIT chain + half starts at row half h of its chain (SPLIT 1: the whole
+// chain).  A row of weight 0 (w given) becomes NaN: not part of the weighted sample, it sorts last, whatever it holds.
+template <typename T, int SPLIT>
+__global__ __launch_bounds__(256) void bf_columns_kernel(long n_el, long h, long ldw, long ldr, const T *__restrict__ x, int nb, int mode,
+                                                        const double *__restrict__ c, const double *__restrict__ w,
+                                                        double *__restrict__ out) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= n_el) return;
     const int b = (int)(e & (DG_B - 1));
-    const long row = e / DG_B;           // j h + i; split chain j = 2 chain + half starts at row half h of its chain
+    const long row = e / DG_B;           // j h + i
     const long j = row / h, i = row - j * h;
     double v = 0.;
     if (b < nb) {
-        v = (double)x[(j >> 1) * ldw + ((j & 1) * h + i) * ldr + b];
+        v = (double)x[(j / SPLIT) * ldw + ((j % SPLIT) * h + i) * ldr + b];
         if (mode == BFHIP_DIAG_FOLD) v = fabs(v - c[b]);
         else if (mode == BFHIP_DIAG_BELOW) v = v <= c[b] ? 1. : 0.;   // (a NaN compares false; such a column is reported as NaN)
+        if (w && w[row] == 0.) v = __builtin_nan("");
     }
     out[e] = v;
+}
+
+template <typename T>
+static void bf_columns_typed(hipStream_t st, int split, long n_el, long h, long ldw, long ldr, const T *x, int nb, int mode,
+                             const double *c, const double *w, double *out) {
+    const dim3 grid((unsigned)((n_el + 255) / 256));
+    if (split == 2) hipLaunchKernelGGL((bf_columns_kernel<T, 2>), grid, dim3(256), 0, st, n_el, h, ldw, ldr, x, nb, mode, c, w, out);
+    else hipLaunchKernelGGL((bf_columns_kernel<T, 1>), grid, dim3(256), 0, st, n_el, h, ldw, ldr, x, nb, mode, c, w, out);
+}
+
+int bf_columns_launch(bfhip_ctx *ctx, int split, long n_el, long h, long ldw, long ldr, const void *x, int is_f32, long off, int nb,
+                      int mode, const double *c, const double *w, double *out) {
+    if (is_f32) bf_columns_typed(ctx->stream, split, n_el, h, ldw, ldr, (const float *)x + off, nb, mode, c, w, out);
+    else bf_columns_typed(ctx->stream, split, n_el, h, ldw, ldr, (const double *)x + off, nb, mode, c, w, out);
+    BF_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 extern "C" int bfhip_diag_columns(bfhip_ctx *ctx, int n_chain, long h, long ldw, long ldr, const void *x, int is_f32, long since,
@@ -46,15 +65,7 @@ extern "C" int bfhip_diag_columns(bfhip_ctx *ctx, int n_chain, long h, long ldw,
     const long n_el = 2L * n_chain * h * DG_B, nblk = (n_el + 255) / 256;
     if (2L * n_chain * h > 0x7fffffffL || nblk > 0x7fffffffL)
         return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_diag_columns: more than 2^31-1 values per column");
-    const long off = since * ldr + k0;
-    if (is_f32)
-        hipLaunchKernelGGL(bf_diag_columns_kernel<float>, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, n_el, h, ldw, ldr,
-                           (const float *)x + off, nb, mode, c, out);
-    else
-        hipLaunchKernelGGL(bf_diag_columns_kernel<double>, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, n_el, h, ldw, ldr,
-                           (const double *)x + off, nb, mode, c, out);
-    BF_HIP_CHECK(hipGetLastError());
-    return 0;
+    return bf_columns_launch(ctx, 2, n_el, h, ldw, ldr, x, is_f32, since * ldr + k0, nb, mode, c, nullptr, out);
 }
 
 // ---- extent: one workgroup per split chain, 16 columns x 16 time slices; min and max are exact in any order ---------------------------
@@ -73,10 +84,8 @@ __global__ __launch_bounds__(256) void bf_diag_extent_kernel(long h, const doubl
     mx[threadIdx.x] = e;
     __syncthreads();
     if (sl == 0) {
-        for (int i = 1; i < 256 / DG_B; ++i) {
-            a = fmin(a, mn[i * DG_B + b]);
-            e = fmax(e, mx[i * DG_B + b]);
-        }
+        a = bf_slice_fold(a, 1, mn, b, BfMin());
+        e = bf_slice_fold(e, 1, mx, b, BfMax());
         lo[(long)blockIdx.x * DG_B + b] = a;
         hi[(long)blockIdx.x * DG_B + b] = e;
     }
@@ -92,35 +101,12 @@ extern "C" int bfhip_diag_extent(bfhip_ctx *ctx, int n_series, long h, const dou
 }
 
 // ---- sort of one column ----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void bf_diag_keys_kernel(long n, const double *__restrict__ series, int b, uint64_t *__restrict__ keys,
-                                                          uint32_t *__restrict__ idx) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) {
-        keys[i] = bf_order_key(series[i * DG_B + b]);
-        idx[i] = (uint32_t)i;
-    }
-}
-
 extern "C" int bfhip_diag_sort(bfhip_ctx *ctx, long n, const double *series, int b, uint64_t *keys_sorted, uint32_t *order) {
     BfDeviceGuard dev_guard(ctx);
     if (!ctx || n < 1 || !series || b < 0 || b >= DG_B || !keys_sorted || !order)
         return bf_set_error(BFHIP_ERR_ARG, "bfhip_diag_sort: invalid argument");
     if (n > 0x7fffffffL) return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_diag_sort: more than 2^31-1 elements");
-    size_t tmp = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const uint32_t *)nullptr,
-                                             (uint32_t *)nullptr, (size_t)n, 0, 64, ctx->stream);
-    if (e != hipSuccess) return bf_set_error(BFHIP_ERR_HIP, "rocprim::radix_sort_pairs (size query): %s", hipGetErrorString(e));
-    // unsorted keys and indices live in the context's workspace, next to rocPRIM's temporary storage (as bfhip_sort_keys)
-    const size_t kb = ((size_t)n * 8 + 255) / 256 * 256, ib = ((size_t)n * 4 + 255) / 256 * 256;
-    if (int rc = bf_grow(ctx, &ctx->scratch, &ctx->scratch_bytes, kb + ib + tmp)) return rc;
-    uint64_t *k0 = (uint64_t *)ctx->scratch;
-    uint32_t *i0 = (uint32_t *)((char *)ctx->scratch + kb);
-    void *t = (char *)ctx->scratch + kb + ib;
-    hipLaunchKernelGGL(bf_diag_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, series, b, k0, i0);
-    BF_HIP_CHECK(hipGetLastError());
-    e = rocprim::radix_sort_pairs(t, tmp, k0, keys_sorted, i0, order, (size_t)n, 0, 64, ctx->stream);  // stable
-    if (e != hipSuccess) return bf_set_error(BFHIP_ERR_HIP, "rocprim::radix_sort_pairs: %s", hipGetErrorString(e));
-    return 0;
+    return bf_sort_column(ctx, n, series, DG_B, b, keys_sorted, order);
 }
 
 // ---- ranks with ties -> normal scores ----------------------------------------------------------------------------------------------

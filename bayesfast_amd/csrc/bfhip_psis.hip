@@ -13,7 +13,7 @@
 // workgroups' partial results the same way.  The shape depends on n alone, so the same input gives the same bits, and a column's
 // sums never see its neighbours.  All of it is bound by HBM reads (8 to 16 bytes per element and pass); the transcendental work
 // of the tail fit is (30 + sqrt M) M log1p, M <= 3 sqrt n.  64-bit offsets throughout.
-#include "bfhip_common.h"
+#include "bfhip_block.h"
 
 #define PS_T 256        // threads per workgroup, everywhere in this file
 #define PS_MAXB 1024    // workgroups of a first-level reduction (they stride over the data beyond PS_T * PS_MAXB elements)
@@ -22,29 +22,8 @@
 #define WS_ROWS (PS_T / WS_B)          // row slices of a workgroup of the column reductions
 #define WS_ITEMS 8                     // consecutive sorted positions per thread of the scan
 #define WS_TILE (PS_T * WS_ITEMS)      // sorted positions per workgroup of the scan
-static_assert(WS_B == 16 && WS_ROWS == 16, "the column reductions take the column with a mask and the slice with a shift");
+static_assert(WS_B == 16 && WS_ROWS == BF_SLICES, "the column reductions take the column with a mask and the slice with a shift");
 static_assert(BFHIP_WSTAT_WORK >= 4 * PS_MAXB * WS_B, "bfhip_wstat_moments keeps up to four partial arrays");
-
-// the value behind an order-preserving key (bf_order_key): -0 comes back as +0, every NaN as one NaN
-__device__ inline double ps_key_value(uint64_t k) {
-    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
-// Halving tree over the workgroup's PS_T values; the result in every thread.  op 0: sum, 1: max, 2: min.
-template <int OP>
-__device__ inline double ps_block_reduce(double v, double *red) {
-    __syncthreads();   // (red may still be read from the previous reduction)
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = PS_T / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            const double a = red[threadIdx.x], b = red[threadIdx.x + o];
-            red[threadIdx.x] = OP == 0 ? a + b : (OP == 1 ? fmax(a, b) : fmin(a, b));
-        }
-        __syncthreads();
-    }
-    return red[0];
-}
 
 static inline int ps_grid(long n, long per_block) {
     const long g = (n + per_block - 1) / per_block;
@@ -63,8 +42,8 @@ __global__ __launch_bounds__(PS_T) void ps_ratio_kernel(long n, const double *__
         if (v != v || v == __builtin_inf()) bad = 1.;
         else mx = fmax(mx, v);
     }
-    mx = ps_block_reduce<1>(mx, red);
-    bad = ps_block_reduce<1>(bad, red);
+    mx = bf_block_reduce<PS_T>(mx, red, BfMax());
+    bad = bf_block_reduce<PS_T>(bad, red, BfMax());
     if (threadIdx.x == 0) {
         part[blockIdx.x] = mx;
         part[PS_MAXB + blockIdx.x] = bad;
@@ -78,8 +57,8 @@ __global__ __launch_bounds__(PS_T) void ps_max_kernel(int nb, const double *__re
         mx = fmax(mx, part[i]);
         bad = fmax(bad, part[PS_MAXB + i]);
     }
-    mx = ps_block_reduce<1>(mx, red);
-    bad = ps_block_reduce<1>(bad, red);
+    mx = bf_block_reduce<PS_T>(mx, red, BfMax());
+    bad = bf_block_reduce<PS_T>(bad, red, BfMax());
     if (threadIdx.x == 0) {
         out8[6] = mx;
         out8[7] = (bad != 0. || mx == -__builtin_inf()) ? 1. : 0.;
@@ -92,20 +71,20 @@ __global__ __launch_bounds__(PS_T) void ps_shift_kernel(long n, const double *__
 }
 
 // exceedance of sorted tail position i over the cut
-__device__ inline double ps_exceed(const uint64_t *tail, long i, double ecut) { return exp(ps_key_value(tail[i])) - ecut; }
+__device__ inline double ps_exceed(const uint64_t *tail, long i, double ecut) { return exp(bf_order_value(tail[i])) - ecut; }
 
 // workgroup j: theta_j and k_j = mean_i log1p(-theta_j x_i)
 __global__ __launch_bounds__(PS_T) void ps_theta_kernel(long n, long M, int m, const uint64_t *__restrict__ ks, double *__restrict__ kj,
                                                        double *__restrict__ thj) {
     __shared__ double red[PS_T];
     const uint64_t *tail = ks + (n - M);
-    const double ecut = exp(ps_key_value(ks[n - M - 1]));
+    const double ecut = exp(bf_order_value(ks[n - M - 1]));
     const double xn = ps_exceed(tail, M - 1, ecut);
     const double xq = ps_exceed(tail, (long)floor((double)M / 4. + 0.5) - 1, ecut);
     const double th = 1. / xn + (1. - sqrt((double)m / ((double)(blockIdx.x + 1) - 0.5))) / (3. * xq);
     double s = 0.;
     for (long i = threadIdx.x; i < M; i += PS_T) s += log1p(-th * ps_exceed(tail, i, ecut));
-    s = ps_block_reduce<0>(s, red);
+    s = bf_block_reduce<PS_T>(s, red, BfSum());
     if (threadIdx.x == 0) {
         kj[blockIdx.x] = s / (double)M;
         thj[blockIdx.x] = th;
@@ -118,7 +97,7 @@ __global__ __launch_bounds__(PS_T) void ps_fit_kernel(long n, long M, int m, con
     __shared__ double red[PS_T], L[PS_MAXM], om[PS_MAXM];
     __shared__ double th_s;
     const uint64_t *tail = ks + (n - M);
-    const double cut = ps_key_value(ks[n - M - 1]), ecut = exp(cut);
+    const double cut = bf_order_value(ks[n - M - 1]), ecut = exp(cut);
     for (int j = threadIdx.x; j < m; j += PS_T) L[j] = (double)M * (log(-thj[j] / kj[j]) - kj[j] - 1.);
     __syncthreads();
     for (int j = threadIdx.x; j < m; j += PS_T) {
@@ -136,7 +115,7 @@ __global__ __launch_bounds__(PS_T) void ps_fit_kernel(long n, long M, int m, con
     const double th = th_s;
     double s = 0.;
     for (long i = threadIdx.x; i < M; i += PS_T) s += log1p(-th * ps_exceed(tail, i, ecut));
-    s = ps_block_reduce<0>(s, red);
+    s = bf_block_reduce<PS_T>(s, red, BfSum());
     if (threadIdx.x == 0) {
         const double k = s / (double)M;
         const bool flat = !(ps_exceed(tail, M - 1, ecut) > 0.);   // no spread in the tail: nothing to fit
@@ -151,7 +130,7 @@ __global__ __launch_bounds__(PS_T) void ps_fit_kernel(long n, long M, int m, con
 __global__ void ps_nofit_kernel(long n, long M, const uint64_t *__restrict__ ks, double *__restrict__ out8) {
     out8[0] = __builtin_inf();
     out8[1] = __builtin_nan("");
-    out8[3] = ps_key_value(ks[n - M - 1]);
+    out8[3] = bf_order_value(ks[n - M - 1]);
     out8[7] = (double)((int)out8[7] | 2);
 }
 
@@ -175,8 +154,8 @@ __global__ __launch_bounds__(PS_T) void ps_lse_kernel(long n, const double *__re
         s1 += exp(v);
         s2 += exp(2. * v);
     }
-    s1 = ps_block_reduce<0>(s1, red);
-    s2 = ps_block_reduce<0>(s2, red);
+    s1 = bf_block_reduce<PS_T>(s1, red, BfSum());
+    s2 = bf_block_reduce<PS_T>(s2, red, BfSum());
     if (threadIdx.x == 0) {
         part[blockIdx.x] = s1;
         part[PS_MAXB + blockIdx.x] = s2;
@@ -191,8 +170,8 @@ __global__ __launch_bounds__(PS_T) void ps_lse_final_kernel(long n, long M, int 
         s1 += part[i];
         s2 += part[PS_MAXB + i];
     }
-    s1 = ps_block_reduce<0>(s1, red);
-    s2 = ps_block_reduce<0>(s2, red);
+    s1 = bf_block_reduce<PS_T>(s1, red, BfSum());
+    s2 = bf_block_reduce<PS_T>(s2, red, BfSum());
     if (threadIdx.x == 0) {
         const double nan = __builtin_nan("");
         const bool bad = ((int)out8[7] & 1) != 0;
@@ -248,22 +227,7 @@ extern "C" int bfhip_psis(bfhip_ctx *ctx, long n, const double *logp, const doub
 }
 
 // ==== the weighted table ==============================================================================================================
-// columns: element e = (row, column b), b fastest; row = chain n_draw + draw
-template <typename T>
-__global__ __launch_bounds__(PS_T) void ws_columns_kernel(long n_el, long n_draw, long ldw, long ldr, const T *__restrict__ x, int nb,
-                                                         const double *__restrict__ w, double *__restrict__ out) {
-    const long e = (long)blockIdx.x * PS_T + threadIdx.x;
-    if (e >= n_el) return;
-    const int b = (int)(e & (WS_B - 1));
-    const long row = e / WS_B, c = row / n_draw, i = row - c * n_draw;
-    double v = 0.;
-    if (b < nb) {
-        v = (double)x[c * ldw + i * ldr + b];
-        if (w && w[row] == 0.) v = __builtin_nan("");   // not part of the weighted sample: sorts last, whatever it holds
-    }
-    out[e] = v;
-}
-
+// columns: element e = (row, column b), b fastest; row = chain n_draw + draw.  The gather is bfhip_diag.hip's, without the split.
 extern "C" int bfhip_wstat_columns(bfhip_ctx *ctx, int n_chain, long n_draw, long ldw, long ldr, const void *x, int is_f32, long since,
                                    int k0, int nb, const double *w, double *out) {
     BfDeviceGuard dev_guard(ctx);
@@ -273,15 +237,7 @@ extern "C" int bfhip_wstat_columns(bfhip_ctx *ctx, int n_chain, long n_draw, lon
     const long n_el = (long)n_chain * n_draw * WS_B, nblk = (n_el + PS_T - 1) / PS_T;
     if ((long)n_chain * n_draw > 0x7fffffffL || nblk > 0x7fffffffL)
         return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_wstat_columns: more than 2^31-1 values per column");
-    const long off = since * ldr + k0;
-    if (is_f32)
-        hipLaunchKernelGGL(ws_columns_kernel<float>, dim3((unsigned)nblk), dim3(PS_T), 0, ctx->stream, n_el, n_draw, ldw, ldr,
-                           (const float *)x + off, nb, w, out);
-    else
-        hipLaunchKernelGGL(ws_columns_kernel<double>, dim3((unsigned)nblk), dim3(PS_T), 0, ctx->stream, n_el, n_draw, ldw, ldr,
-                           (const double *)x + off, nb, w, out);
-    BF_HIP_CHECK(hipGetLastError());
-    return 0;
+    return bf_columns_launch(ctx, 1, n_el, n_draw, ldw, ldr, x, is_f32, since * ldr + k0, nb, BFHIP_DIAG_PLAIN, nullptr, w, out);
 }
 
 // ---- sums of the weights: sum w, sum w^2, the number of non-zero weights, a flag for a negative or non-finite one ----------------------
@@ -295,10 +251,10 @@ __global__ __launch_bounds__(PS_T) void ws_wsum_kernel(long n, const double *__r
         if (v != 0.) cnt += 1.;
         if (!(v >= 0.) || v == __builtin_inf()) bad = 1.;
     }
-    s1 = ps_block_reduce<0>(s1, red);
-    s2 = ps_block_reduce<0>(s2, red);
-    cnt = ps_block_reduce<0>(cnt, red);   // (whole numbers below 2^31: exact)
-    bad = ps_block_reduce<1>(bad, red);
+    s1 = bf_block_reduce<PS_T>(s1, red, BfSum());
+    s2 = bf_block_reduce<PS_T>(s2, red, BfSum());
+    cnt = bf_block_reduce<PS_T>(cnt, red, BfSum());   // (whole numbers below 2^31: exact)
+    bad = bf_block_reduce<PS_T>(bad, red, BfMax());
     if (threadIdx.x == 0) {
         part[blockIdx.x] = s1;
         part[PS_MAXB + blockIdx.x] = s2;
@@ -316,10 +272,10 @@ __global__ __launch_bounds__(PS_T) void ws_wsum_final_kernel(int nb, const doubl
         cnt += part[2 * PS_MAXB + i];
         bad = fmax(bad, part[3 * PS_MAXB + i]);
     }
-    s1 = ps_block_reduce<0>(s1, red);
-    s2 = ps_block_reduce<0>(s2, red);
-    cnt = ps_block_reduce<0>(cnt, red);
-    bad = ps_block_reduce<1>(bad, red);
+    s1 = bf_block_reduce<PS_T>(s1, red, BfSum());
+    s2 = bf_block_reduce<PS_T>(s2, red, BfSum());
+    cnt = bf_block_reduce<PS_T>(cnt, red, BfSum());
+    bad = bf_block_reduce<PS_T>(bad, red, BfMax());
     if (threadIdx.x == 0) {
         wsum[0] = s1;
         wsum[1] = s2;
@@ -329,6 +285,16 @@ __global__ __launch_bounds__(PS_T) void ws_wsum_final_kernel(int nb, const doubl
 }
 
 // ---- column moments: thread (slice sl, column b) walks rows sl, sl + 16 G, ...; PASS 1: sum w x, min, max; PASS 2: the centred sums -------
+// Slice 0 folds the other slices' (sum, min or sum, max) onto its own, slice by slice: bf_slice_fold's order, the three in one
+// loop (three calls of it keep fifteen more LDS reads in flight and take up to seven more registers)
+template <int PASS>
+__device__ inline void ws_fold(double &a0, double &a1, double &a2, const double *r0, const double *r1, const double *r2, int b) {
+    for (int i = 1; i < WS_ROWS; ++i) {
+        a0 += r0[i * WS_B + b];
+        a1 = PASS == 1 ? fmin(a1, r1[i * WS_B + b]) : a1 + r1[i * WS_B + b];
+        a2 = fmax(a2, r2[i * WS_B + b]);
+    }
+}
 template <int PASS>
 __global__ __launch_bounds__(PS_T) void ws_moments_kernel(long n, const double *__restrict__ series, const double *__restrict__ w,
                                                          const double *__restrict__ mean, double *__restrict__ part) {
@@ -355,11 +321,7 @@ __global__ __launch_bounds__(PS_T) void ws_moments_kernel(long n, const double *
     r2[threadIdx.x] = a2;
     __syncthreads();
     if (sl == 0) {
-        for (int i = 1; i < WS_ROWS; ++i) {
-            a0 += r0[i * WS_B + b];
-            a1 = PASS == 1 ? fmin(a1, r1[i * WS_B + b]) : a1 + r1[i * WS_B + b];
-            a2 = fmax(a2, r2[i * WS_B + b]);
-        }
+        ws_fold<PASS>(a0, a1, a2, r0, r1, r2, b);
         part[(long)blockIdx.x * WS_B + b] = a0;
         part[((long)PS_MAXB + blockIdx.x) * WS_B + b] = a1;
         if (PASS == 1) part[((long)2 * PS_MAXB + blockIdx.x) * WS_B + b] = a2;
@@ -383,11 +345,7 @@ __global__ __launch_bounds__(PS_T) void ws_moments_final_kernel(int nb, const do
     r2[threadIdx.x] = a2;
     __syncthreads();
     if (sl == 0) {
-        for (int i = 1; i < WS_ROWS; ++i) {
-            a0 += r0[i * WS_B + b];
-            a1 = PASS == 1 ? fmin(a1, r1[i * WS_B + b]) : a1 + r1[i * WS_B + b];
-            a2 = fmax(a2, r2[i * WS_B + b]);
-        }
+        ws_fold<PASS>(a0, a1, a2, r0, r1, r2, b);
         if (PASS == 1) {
             out[b] = a0;
             out[3 * WS_B + b] = a1;
@@ -515,7 +473,7 @@ __global__ void ws_quantiles_kernel(long n, const uint64_t *__restrict__ ks, con
     double val = __builtin_nan("");
     const double cnt = wsum[2];
     const long np = cnt >= 1. && cnt <= (double)n ? (long)cnt : 0;
-    if (np == 1) val = ps_key_value(ks[0]);
+    if (np == 1) val = bf_order_value(ks[0]);
     else if (np > 1) {
         const double q = probs[i];
         const double m0 = cum[0] - 0.5 * w[order[0]], den = (cum[np - 1] - 0.5 * w[order[np - 1]]) - m0;
@@ -526,10 +484,10 @@ __global__ void ws_quantiles_kernel(long n, const uint64_t *__restrict__ ks, con
                 if (ws_pos(mid, order, w, cum, m0, den) <= q) lo = mid;
                 else hi = mid - 1;
             }
-            const double a = ps_key_value(ks[lo]);
+            const double a = bf_order_value(ks[lo]);
             if (lo == np - 1) val = a;
             else {
-                const double c = ps_key_value(ks[lo + 1]), pk = ws_pos(lo, order, w, cum, m0, den);
+                const double c = bf_order_value(ks[lo + 1]), pk = ws_pos(lo, order, w, cum, m0, den);
                 const double t = (q - pk) / (ws_pos(lo + 1, order, w, cum, m0, den) - pk), d = c - a;
                 val = t >= 0.5 ? c - d * (1. - t) : a + d * t;
             }

@@ -5,15 +5,39 @@
 // device radix sort (a plain library primitive, like rocBLAS for a plain GEMM).
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
-#include "bfhip_common.h"
+#include "bfhip_block.h"
 
-__global__ void bf_keys_iota_kernel(long n, const double *__restrict__ a, uint64_t *__restrict__ keys, int64_t *__restrict__ idx) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+// keys[i] = the order key of a[i * stride + col]; idx[i] = i where a permutation is wanted
+template <typename Index>
+__global__ __launch_bounds__(256) void bf_keys_kernel(long n, const double *__restrict__ a, long stride, int col,
+                                                     uint64_t *__restrict__ keys, Index *__restrict__ idx) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) {
-        keys[i] = bf_order_key(a[i]);
-        idx[i] = i;
+        keys[i] = bf_order_key(a[i * stride + col]);
+        if (idx) idx[i] = (Index)i;
     }
 }
+
+template <typename Index>
+int bf_sort_column(bfhip_ctx *ctx, long n, const double *a, long stride, int col, uint64_t *keys_sorted, Index *order) {
+    size_t tmp = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const Index *)nullptr,
+                                             (Index *)nullptr, (size_t)n, 0, 64, ctx->stream);
+    if (e != hipSuccess) return bf_set_error(BFHIP_ERR_HIP, "rocprim::radix_sort_pairs (size query): %s", hipGetErrorString(e));
+    // unsorted keys and indices live in the context's workspace, next to rocPRIM's temporary storage
+    const size_t kb = ((size_t)n * 8 + 255) / 256 * 256, ib = ((size_t)n * sizeof(Index) + 255) / 256 * 256;
+    if (int rc = bf_grow(ctx, &ctx->scratch, &ctx->scratch_bytes, kb + ib + tmp)) return rc;
+    uint64_t *k0 = (uint64_t *)ctx->scratch;
+    Index *i0 = (Index *)((char *)ctx->scratch + kb);
+    void *t = (char *)ctx->scratch + kb + ib;
+    hipLaunchKernelGGL(bf_keys_kernel<Index>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, a, stride, col, k0, i0);
+    BF_HIP_CHECK(hipGetLastError());
+    e = rocprim::radix_sort_pairs(t, tmp, k0, keys_sorted, i0, order, (size_t)n, 0, 64, ctx->stream);  // stable
+    if (e != hipSuccess) return bf_set_error(BFHIP_ERR_HIP, "rocprim::radix_sort_pairs: %s", hipGetErrorString(e));
+    return 0;
+}
+template int bf_sort_column<int64_t>(bfhip_ctx *, long, const double *, long, int, uint64_t *, int64_t *);
+template int bf_sort_column<uint32_t>(bfhip_ctx *, long, const double *, long, int, uint64_t *, uint32_t *);
 
 extern "C" int bfhip_sort_keys(bfhip_ctx *ctx, long n, const double *a, uint64_t *keys_sorted, int64_t *order) {
     BfDeviceGuard dev_guard(ctx);
@@ -21,33 +45,15 @@ extern "C" int bfhip_sort_keys(bfhip_ctx *ctx, long n, const double *a, uint64_t
         return bf_set_error(BFHIP_ERR_ARG, "bfhip_sort_keys: invalid argument");
     if (n == 0) return 0;
     if (n > 0x7fffffffL) return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_sort_keys: more than 2^31-1 elements");
-    size_t tmp = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const int64_t *)nullptr,
-                                             (int64_t *)nullptr, (size_t)n, 0, 64, ctx->stream);
-    if (e != hipSuccess) return bf_set_error(BFHIP_ERR_HIP, "rocprim::radix_sort_pairs (size query): %s", hipGetErrorString(e));
-    // unsorted keys and indices live in the context's workspace, next to rocPRIM's temporary storage
-    const size_t kb = ((size_t)n * 8 + 255) / 256 * 256;
-    if (int rc = bf_grow(ctx, &ctx->scratch, &ctx->scratch_bytes, 2 * kb + tmp)) return rc;
-    uint64_t *k0 = (uint64_t *)ctx->scratch;
-    int64_t *i0 = (int64_t *)((char *)ctx->scratch + kb);
-    void *t = (char *)ctx->scratch + 2 * kb;
-    hipLaunchKernelGGL(bf_keys_iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, a, k0, i0);
-    BF_HIP_CHECK(hipGetLastError());
-    e = rocprim::radix_sort_pairs(t, tmp, k0, keys_sorted, i0, order, (size_t)n, 0, 64, ctx->stream);  // stable
-    if (e != hipSuccess) return bf_set_error(BFHIP_ERR_HIP, "rocprim::radix_sort_pairs: %s", hipGetErrorString(e));
-    return 0;
-}
-
-__global__ void bf_order_keys_kernel(long n, const double *__restrict__ a, uint64_t *__restrict__ keys) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) keys[i] = bf_order_key(a[i]);
+    return bf_sort_column(ctx, n, a, 1, 0, keys_sorted, order);
 }
 
 extern "C" int bfhip_order_keys(bfhip_ctx *ctx, long n, const double *a, uint64_t *keys) {
     BfDeviceGuard dev_guard(ctx);
     if (!ctx || n < 0 || (n > 0 && (!a || !keys))) return bf_set_error(BFHIP_ERR_ARG, "bfhip_order_keys: invalid argument");
     if (n == 0) return 0;
-    hipLaunchKernelGGL(bf_order_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, a, keys);
+    hipLaunchKernelGGL(bf_keys_kernel<int64_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, a, 1L, 0, keys,
+                       (int64_t *)nullptr);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -90,13 +96,8 @@ __global__ void bf_iw_exp_kernel(long n, const double *__restrict__ logp, const 
         w[i] = v;
         s += v;
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+    s = bf_block_reduce<256, true>(s, red, BfSum());
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 __global__ void bf_iw_clip_kernel(long n, const double *__restrict__ w, const double *__restrict__ partial, int n_part, double k_trunc,

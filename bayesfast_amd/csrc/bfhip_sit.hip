@@ -15,7 +15,7 @@
 // HBM-/ALU-bound elementwise and reduction work in float64; every reduction has a fixed order (per-block partial sums
 // combined by one thread), so results do not depend on the launch.
 #include <cmath>
-#include "bfhip_common.h"
+#include "bfhip_block.h"
 #include "bfhip_ndtri.h"
 
 // ---- KDE cdf -----------------------------------------------------------------------------------------------------
@@ -44,14 +44,8 @@ __global__ __launch_bounds__(KDE_TH) void bf_kde_cdf_kernel(int n, int m, const 
     __shared__ double red[KDE_TH];
 #pragma unroll
     for (int t = 0; t < KDE_KP; ++t) {
-        red[threadIdx.x] = acc[t];
-        __syncthreads();
-        for (int o = KDE_TH / 2; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0 && i0 + t < m) partial[((size_t)j * n_split + sp) * m + i0 + t] = red[0];
-        __syncthreads();
+        const double s = bf_block_reduce<KDE_TH, true>(acc[t], red, BfSum());
+        if (threadIdx.x == 0 && i0 + t < m) partial[((size_t)j * n_split + sp) * m + i0 + t] = s;
     }
 }
 
@@ -185,7 +179,7 @@ __device__ inline double bf_log_sigmoid(double x) {  // x - logaddexp(x, 0) = -s
     return (x < 0.) ? x - log1p(exp(x)) : -log1p(exp(-x));
 }
 __global__ __launch_bounds__(256) void bf_lse_sig_kernel(long n, const double *__restrict__ a, double s, double *__restrict__ part) {
-    __shared__ double rm[256], rs[256];
+    __shared__ double red[2 * 256];
     double mx = -INFINITY, sm = 0.;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const double t = bf_log_sigmoid(s + a[i]);
@@ -193,19 +187,14 @@ __global__ __launch_bounds__(256) void bf_lse_sig_kernel(long n, const double *_
         else if (t > -INFINITY) sm += exp(t - mx);
         else if (t != t) sm = NAN;                            // NaN propagates through the sums
     }
-    rm[threadIdx.x] = mx;
-    rs[threadIdx.x] = sm;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            const double m1 = rm[threadIdx.x], m2 = rm[threadIdx.x + o], s1 = rs[threadIdx.x], s2 = rs[threadIdx.x + o];
-            const double mm = m1 > m2 ? m1 : m2;
-            rs[threadIdx.x] = (mm == -INFINITY) ? s1 + s2 : s1 * exp(m1 - mm) + s2 * exp(m2 - mm);
-            rm[threadIdx.x] = mm;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { part[2 * blockIdx.x] = rm[0]; part[2 * blockIdx.x + 1] = rs[0]; }
+    double ms[2] = {mx, sm};
+    bf_block_tree<256, 2>(ms, red, [](double *p, const double *q) {   // (this kernel's own merge: unlike bf_ms_merge, a max of +inf is NaN)
+        const double m1 = p[0], m2 = q[0], s1 = p[1], s2 = q[1];
+        const double mm = m1 > m2 ? m1 : m2;
+        p[1] = (mm == -INFINITY) ? s1 + s2 : s1 * exp(m1 - mm) + s2 * exp(m2 - mm);
+        p[0] = mm;
+    });
+    if (threadIdx.x == 0) { part[2 * blockIdx.x] = ms[0]; part[2 * blockIdx.x + 1] = ms[1]; }
 }
 __global__ void bf_lse_combine_kernel(int nb_a, int nb_b, const double *__restrict__ part, double *__restrict__ out) {
     if (threadIdx.x >= 2 || blockIdx.x != 0) return;
@@ -232,22 +221,14 @@ extern "C" int bfhip_bridge_sums(bfhip_ctx *ctx, long n_a, const double *a, long
     return 0;
 }
 
-// numpy.logaddexp
-__device__ inline double bf_lae(double x, double y) {
-    if (x == y) return x + 0.6931471805599453094;
-    const double t = x - y;
-    if (t > 0) return x + log1p(exp(-t));
-    if (t <= 0) return y + log1p(exp(t));
-    return t;
-}
 // evidence/bridge.py:52-57: f1 over the q samples, f2 over the p samples
 __global__ void bf_bridge_terms_kernel(long n_p, const double *__restrict__ lpp, const double *__restrict__ lqp, long n_q,
                                        const double *__restrict__ lpq, const double *__restrict__ lqq, double logr, double *__restrict__ f1,
                                        double *__restrict__ f2) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const double lp = log((double)n_p / (double)(n_p + n_q)), lq = log((double)n_q / (double)(n_p + n_q));
-    if (i < n_q) f1[i] = exp(lpq[i] - logr - bf_lae(lpq[i] - logr + lp, lqq[i] + lq));
-    if (i < n_p) f2[i] = exp(lqp[i] - bf_lae(lpp[i] - logr + lp, lqp[i] + lq));
+    if (i < n_q) f1[i] = exp(lpq[i] - logr - bf_logaddexp(lpq[i] - logr + lp, lqq[i] + lq));
+    if (i < n_p) f2[i] = exp(lqp[i] - bf_logaddexp(lpp[i] - logr + lp, lqp[i] + lq));
 }
 
 extern "C" int bfhip_bridge_terms(bfhip_ctx *ctx, long n_p, const double *logp_p, const double *logq_p, long n_q, const double *logp_q,
@@ -276,19 +257,9 @@ __device__ inline void bf_ms_merge(double &m1, double &s1, double m2, double s2)
     s1 = (m1 == mm ? s1 : s1 * exp(m1 - mm)) + (m2 == mm ? s2 : s2 * exp(m2 - mm));
     m1 = mm;
 }
-__device__ inline void bf_ms_block(double mx, double sm, double *rm, double *rs) {  // -> rm[0], rs[0]
-    rm[threadIdx.x] = mx;
-    rs[threadIdx.x] = sm;
-    __syncthreads();
-    for (int o = LME_TH / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            double m = rm[threadIdx.x], s = rs[threadIdx.x];
-            bf_ms_merge(m, s, rm[threadIdx.x + o], rs[threadIdx.x + o]);
-            rm[threadIdx.x] = m;
-            rs[threadIdx.x] = s;
-        }
-        __syncthreads();
-    }
+// the workgroup's LME_TH (max, sum) pairs -> one, in ms of every thread; red: 2 LME_TH doubles
+__device__ inline void bf_ms_block(double *ms, double *red) {
+    bf_block_tree<LME_TH, 2>(ms, red, [](double *p, const double *q) { bf_ms_merge(p[0], p[1], q[0], q[1]); });
 }
 // Chan et al.'s pairwise update of (count, mean, M2)
 __device__ inline void bf_welford_merge(double &c1, double &m1, double &q1, double c2, double m2, double q2) {
@@ -299,25 +270,13 @@ __device__ inline void bf_welford_merge(double &c1, double &m1, double &q1, doub
     q1 += q2 + dl * dl * (c1 * c2 / c);
     c1 = c;
 }
-__device__ inline void bf_welford_block(double c, double m, double q, double *rc, double *rm, double *rq) {  // -> rc[0], rm[0], rq[0]
-    rc[threadIdx.x] = c;
-    rm[threadIdx.x] = m;
-    rq[threadIdx.x] = q;
-    __syncthreads();
-    for (int o = LME_TH / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            double c1 = rc[threadIdx.x], m1 = rm[threadIdx.x], q1 = rq[threadIdx.x];
-            bf_welford_merge(c1, m1, q1, rc[threadIdx.x + o], rm[threadIdx.x + o], rq[threadIdx.x + o]);
-            rc[threadIdx.x] = c1;
-            rm[threadIdx.x] = m1;
-            rq[threadIdx.x] = q1;
-        }
-        __syncthreads();
-    }
+// the workgroup's LME_TH (count, mean, M2) triples -> one, in cmq of every thread; red: 3 LME_TH doubles
+__device__ inline void bf_welford_block(double *cmq, double *red) {
+    bf_block_tree<LME_TH, 3>(cmq, red, [](double *p, const double *q) { bf_welford_merge(p[0], p[1], p[2], q[0], q[1], q[2]); });
 }
 __global__ __launch_bounds__(LME_TH) void bf_lme_part_kernel(long n, const double *__restrict__ x, const double *__restrict__ y,
                                                             double *__restrict__ part) {
-    __shared__ double rm[LME_TH], rs[LME_TH];
+    __shared__ double red[2 * LME_TH];
     double mx = -INFINITY, sm = 0.;
     for (long i = (long)blockIdx.x * LME_TH + threadIdx.x; i < n; i += (long)gridDim.x * LME_TH) {
         const double t = x[i] - y[i];
@@ -325,21 +284,23 @@ __global__ __launch_bounds__(LME_TH) void bf_lme_part_kernel(long n, const doubl
         else if (t > -INFINITY) sm += (t == mx) ? 1. : exp(t - mx);
         else if (t != t) sm = NAN;                                  // -inf is a zero weight, NaN propagates
     }
-    bf_ms_block(mx, sm, rm, rs);
-    if (threadIdx.x == 0) { part[2 * blockIdx.x] = rm[0]; part[2 * blockIdx.x + 1] = rs[0]; }
+    double ms[2] = {mx, sm};
+    bf_ms_block(ms, red);
+    if (threadIdx.x == 0) { part[2 * blockIdx.x] = ms[0]; part[2 * blockIdx.x + 1] = ms[1]; }
 }
 // one block of LME_TH threads: thread j merges partials j and j + LME_TH, then the block tree
 __global__ __launch_bounds__(LME_TH) void bf_lme_combine_kernel(int nb, long n, const double *__restrict__ part, double *__restrict__ out3) {
-    __shared__ double rm[LME_TH], rs[LME_TH];
+    __shared__ double red[2 * LME_TH];
     double mx = -INFINITY, sm = 0.;
     for (int b = threadIdx.x; b < nb; b += LME_TH) bf_ms_merge(mx, sm, part[2 * b], part[2 * b + 1]);
-    bf_ms_block(mx, sm, rm, rs);
-    if (threadIdx.x == 0) out3[0] = rm[0] + log(rs[0] / (double)n);  // all -inf: -inf + log(0) = -inf
+    double ms[2] = {mx, sm};
+    bf_ms_block(ms, red);
+    if (threadIdx.x == 0) out3[0] = ms[0] + log(ms[1] / (double)n);  // all -inf: -inf + log(0) = -inf
 }
 __global__ __launch_bounds__(LME_TH) void bf_lme_moments_kernel(long n, const double *__restrict__ x, const double *__restrict__ y,
                                                                const double *__restrict__ out3, double *__restrict__ terms,
                                                                double *__restrict__ part) {
-    __shared__ double rc[LME_TH], rm[LME_TH], rq[LME_TH];
+    __shared__ double red[3 * LME_TH];
     const double L = out3[0];
     double c = 0., m = 0., q = 0.;
     for (long i = (long)blockIdx.x * LME_TH + threadIdx.x; i < n; i += (long)gridDim.x * LME_TH) {
@@ -350,15 +311,17 @@ __global__ __launch_bounds__(LME_TH) void bf_lme_moments_kernel(long n, const do
         m += dl / c;
         q += dl * (f - m);
     }
-    bf_welford_block(c, m, q, rc, rm, rq);
-    if (threadIdx.x == 0) { part[3 * blockIdx.x] = rc[0]; part[3 * blockIdx.x + 1] = rm[0]; part[3 * blockIdx.x + 2] = rq[0]; }
+    double cmq[3] = {c, m, q};
+    bf_welford_block(cmq, red);
+    if (threadIdx.x == 0) { part[3 * blockIdx.x] = cmq[0]; part[3 * blockIdx.x + 1] = cmq[1]; part[3 * blockIdx.x + 2] = cmq[2]; }
 }
 __global__ __launch_bounds__(LME_TH) void bf_lme_moments_combine_kernel(int nb, const double *__restrict__ part, double *__restrict__ out3) {
-    __shared__ double rc[LME_TH], rm[LME_TH], rq[LME_TH];
+    __shared__ double red[3 * LME_TH];
     double c = 0., m = 0., q = 0.;
     for (int b = threadIdx.x; b < nb; b += LME_TH) bf_welford_merge(c, m, q, part[3 * b], part[3 * b + 1], part[3 * b + 2]);
-    bf_welford_block(c, m, q, rc, rm, rq);
-    if (threadIdx.x == 0) { out3[1] = rm[0]; out3[2] = rq[0] / rc[0]; }
+    double cmq[3] = {c, m, q};
+    bf_welford_block(cmq, red);
+    if (threadIdx.x == 0) { out3[1] = cmq[1]; out3[2] = cmq[2] / cmq[0]; }
 }
 
 extern "C" int bfhip_logmeanexp_stats(bfhip_ctx *ctx, long n, const double *x, const double *y, double *out3, double *terms) {
@@ -420,7 +383,6 @@ __global__ __launch_bounds__(64) void bf_small_gemm_kernel(int d, const double *
 // X0 = A / sqrt(|A|_1 |A|_inf) (one workgroup; d <= 1024)
 __global__ __launch_bounds__(256) void bf_ns_scale_kernel(int d, const double *__restrict__ A, double *__restrict__ X) {
     __shared__ double red[256];
-    __shared__ double s_col, s_row;
     double mc = 0., mr = 0.;
     for (int j = threadIdx.x; j < d; j += 256) {
         double c = 0., r = 0.;
@@ -428,16 +390,7 @@ __global__ __launch_bounds__(256) void bf_ns_scale_kernel(int d, const double *_
         mc = c > mc ? c : mc;
         mr = r > mr ? r : mr;
     }
-    red[threadIdx.x] = mc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + o]); __syncthreads(); }
-    if (threadIdx.x == 0) s_col = red[0];
-    __syncthreads();
-    red[threadIdx.x] = mr;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + o]); __syncthreads(); }
-    if (threadIdx.x == 0) s_row = red[0];
-    __syncthreads();
+    const double s_col = bf_block_reduce<256>(mc, red, BfMax()), s_row = bf_block_reduce<256>(mr, red, BfMax());
     const double inv = 1. / sqrt(s_col * s_row);
     for (int i = threadIdx.x; i < d * d; i += 256) X[i] = A[i] * inv;
 }
@@ -450,13 +403,8 @@ __global__ __launch_bounds__(256) void bf_ns_resid_kernel(int d, const double *_
         const double v = fabs(T[i] - ((i / d == i % d) ? 1. : 0.));
         m = (v > m || v != v) ? v : m;   // (NaN propagates)
     }
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { const double u = red[threadIdx.x + o]; if (u > red[threadIdx.x] || u != u) red[threadIdx.x] = u; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) resid[0] = red[0];
+    m = bf_block_reduce<256>(m, red, [](double a, double u) { return (u > a || u != u) ? u : a; });   // (NaN wins)
+    if (threadIdx.x == 0) resid[0] = m;
 }
 
 // The whole iteration as ONE launch: nt x nt single-wave workgroups (all resident: d <= 512), a grid barrier between the two

@@ -8,69 +8,12 @@ import warnings
 
 import numpy as np
 
-from ..transforms.sit import SIT
-from .gbs import _evaluate, _optional_positive
+from .gbs import (_WRONG_LOGP_P, _checked_shape, _checked_sit, _device_density, _device_samples, _draws_from_q, _evaluate,
+                  _host_samples, _optional_positive)
 from .harmonic import harmonic
 from .importance import importance
 
 __all__ = ['GIS', 'GHM']
-
-_WRONG_LOGP_P = 'the logp_p you gave me seems not correct. Will recompute it from logp and x_p.'
-
-
-def _checked_sit(sit):
-    if isinstance(sit, SIT):
-        return sit
-    if sit is None or isinstance(sit, dict):
-        return SIT(**(sit or {}))
-    raise ValueError('invalid value for sit.')
-
-
-def _host_samples(x_p):
-    """(n_call or None, samples as an array (n, d) or (chain, iteration, d)) from a TraceTuple or an array-like."""
-    from ..samplers.sample_trace import TraceTuple
-    if isinstance(x_p, TraceTuple):
-        return x_p.n_call, x_p.get(flatten=False)
-    try:
-        x_p = np.asarray(x_p, dtype=np.float64)
-    except Exception:
-        x_p = None
-    if x_p is None or x_p.ndim not in (2, 3):
-        raise ValueError('invalid value for x_p.')
-    return None, x_p
-
-
-def _checked_shape(x_p):
-    """The number of samples; a single chain loses its chain axis (the halves are then halves of the iterations)."""
-    n_samples = int(np.prod(x_p.shape[:-1]))
-    if x_p.shape[-1] < 2 or n_samples < 2:
-        raise ValueError('invalid shape for x_p.')
-    return n_samples, (x_p[0] if x_p.shape[0] == 1 else x_p)
-
-
-def _device_samples(trace):
-    """The samples of a one-rank TraceTuple after the warm-up as the device tensor (chain, iteration, d) it holds, or None."""
-    import torch
-    from .. import parallel
-    if parallel.world()[1] > 1:
-        return None
-    t = trace.device('samples_original')
-    if not isinstance(t, torch.Tensor) or t.dim() != 3:
-        return None
-    if trace.n_warmup >= trace.i_iter - 1:
-        raise ValueError('since_iter is too large. Nothing to return.')
-    return t[:, trace.n_warmup:]
-
-
-def _device_density(logp):
-    """The ``SurrogateDensity`` whose ``logp`` (or itself) ``logp`` is, or None."""
-    from ..core.density import SurrogateDensity
-    if type(logp) is SurrogateDensity:
-        return logp
-    den = getattr(logp, '__self__', None)
-    if isinstance(den, SurrogateDensity) and getattr(logp, '__func__', None) in (SurrogateDensity.logp, SurrogateDensity.__call__):
-        return den
-    return None
 
 
 class GIS:
@@ -82,16 +25,6 @@ class GIS:
         self.sit = _checked_sit(sit)
         self.n_q = _optional_positive(n_q, int, 'n_q')
         self.f_call = _optional_positive(f_call, float, 'f_call')
-
-    def _draws_from_q(self, n_samples, n_call):
-        if self.n_q is not None:
-            return self.n_q
-        if self.f_call is not None:
-            if n_call is not None:
-                return int(n_call * self.f_call)
-            warnings.warn('f_call should be used only when x_p is a TraceTuple. Using equal-sample allocation for now.',
-                          RuntimeWarning)
-        return n_samples
 
     def run(self, x_p, logp, logp_p=None):
         """x_p: posterior samples (n, d), (chain, iteration, d) or a ``TraceTuple``; logp: the unnormalised log-posterior;
@@ -112,7 +45,7 @@ class GIS:
                 return dev
         n_call, x_p = _host_samples(x_p)
         n_samples, x_p = _checked_shape(x_p)
-        n_q = self._draws_from_q(n_samples, n_call)
+        n_q = _draws_from_q(self.n_q, self.f_call, n_samples, n_call)
         self.sit.fit(data=x_p)
         x_q = self.sit.sample(n_q)[0]
         return importance(_evaluate(logp, x_q), self.sit.logq(x_q))
@@ -129,7 +62,7 @@ class GIS:
         if x_p is None:
             return None
         n_samples, x_p = _checked_shape(x_p)
-        n_q = self._draws_from_q(n_samples, trace.n_call)
+        n_q = _draws_from_q(self.n_q, self.f_call, n_samples, trace.n_call)
         self.sit.fit(data=x_p.reshape(-1, x_p.shape[-1]))
         x_q = self.sit._sample_device(n_q)
         return importance(den.device().logp_and_grad(x_q, True)[0], self.sit._logq_device(x_q))

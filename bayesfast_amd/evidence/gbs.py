@@ -23,6 +23,64 @@ def _optional_positive(value, kind, name):
     return value
 
 
+_WRONG_LOGP_P = 'the logp_p you gave me seems not correct. Will recompute it from logp and x_p.'
+
+
+def _checked_sit(sit):
+    if isinstance(sit, SIT):
+        return sit
+    if sit is None or isinstance(sit, dict):
+        return SIT(**(sit or {}))
+    raise ValueError('invalid value for sit.')
+
+
+def _host_samples(x_p):
+    """(n_call or None, samples as an array (n, d) or (chain, iteration, d)) from a TraceTuple or an array-like."""
+    from ..samplers.sample_trace import TraceTuple
+    if isinstance(x_p, TraceTuple):
+        return x_p.n_call, x_p.get(flatten=False)
+    try:
+        x_p = np.asarray(x_p, dtype=np.float64)
+    except Exception:
+        x_p = None
+    if x_p is None or x_p.ndim not in (2, 3):
+        raise ValueError('invalid value for x_p.')
+    return None, x_p
+
+
+def _checked_shape(x_p):
+    """The number of samples; a single chain loses its chain axis (the halves are then halves of the iterations)."""
+    n_samples = int(np.prod(x_p.shape[:-1]))
+    if x_p.shape[-1] < 2 or n_samples < 2:
+        raise ValueError('invalid shape for x_p.')
+    return n_samples, (x_p[0] if x_p.shape[0] == 1 else x_p)
+
+
+def _device_samples(trace):
+    """The samples of a one-rank TraceTuple after the warm-up as the device tensor (chain, iteration, d) it holds, or None."""
+    import torch
+    from .. import parallel
+    if parallel.world()[1] > 1:
+        return None
+    t = trace.device('samples_original')
+    if not isinstance(t, torch.Tensor) or t.dim() != 3:
+        return None
+    if trace.n_warmup >= trace.i_iter - 1:
+        raise ValueError('since_iter is too large. Nothing to return.')
+    return t[:, trace.n_warmup:]
+
+
+def _device_density(logp):
+    """The ``SurrogateDensity`` whose ``logp`` (or itself) ``logp`` is, or None."""
+    from ..core.density import SurrogateDensity
+    if type(logp) is SurrogateDensity:
+        return logp
+    den = getattr(logp, '__self__', None)
+    if isinstance(den, SurrogateDensity) and getattr(logp, '__func__', None) in (SurrogateDensity.logp, SurrogateDensity.__call__):
+        return den
+    return None
+
+
 def _evaluate(logp, points):
     """logp on an array of points (..., d): in one call when the callable takes a batch, point by point otherwise."""
     lead, d = points.shape[:-1], points.shape[-1]
@@ -39,30 +97,28 @@ def _evaluate(logp, points):
     return values.reshape(lead)
 
 
+def _draws_from_q(n_q, f_call, n_samples, n_call):
+    """How many draws to take from the fitted SIT: ``n_q`` if given, else ``f_call`` times the sampler's density calls (known for
+    a ``TraceTuple`` only), else as many as there are samples."""
+    if n_q is not None:
+        return n_q
+    if f_call is not None:
+        if n_call is not None:
+            return int(n_call * f_call)
+        warnings.warn('f_call should be used only when x_p is a TraceTuple. Using equal-sample allocation for now.',
+                      RuntimeWarning)
+    return n_samples
+
+
 class GBS:
     """``GBS(sit=None, parallel_backend=None, n_q=None, f_call=0.05)`` with the reference's meaning: ``sit`` a ``SIT``, the
     keyword arguments of one, or None; ``n_q`` draws from the fitted SIT, or ``f_call`` times the number of density calls
     the sampler spent when the samples come as a ``TraceTuple``.  ``parallel_backend`` is accepted and ignored."""
 
     def __init__(self, sit=None, parallel_backend=None, n_q=None, f_call=0.05):
-        if isinstance(sit, SIT):
-            self.sit = sit
-        elif sit is None or isinstance(sit, dict):
-            self.sit = SIT(**(sit or {}))
-        else:
-            raise ValueError('invalid value for sit.')
+        self.sit = _checked_sit(sit)
         self.n_q = _optional_positive(n_q, int, 'n_q')
         self.f_call = _optional_positive(f_call, float, 'f_call')
-
-    def _draws_from_q(self, n_samples, n_call):
-        if self.n_q is not None:
-            return self.n_q
-        if self.f_call is not None:
-            if n_call is not None:
-                return int(n_call * self.f_call)
-            warnings.warn('f_call should be used only when x_p is a TraceTuple. Using equal-sample allocation for now.',
-                          RuntimeWarning)
-        return n_samples
 
     def run(self, x_p, logp, logp_p=None):
         """x_p: posterior samples (n, d), (chain, iteration, d) or a ``TraceTuple``; logp: the unnormalised log-posterior;
@@ -79,25 +135,13 @@ class GBS:
 
     def _run(self, x_p, logp, logp_p):
         from ..samplers.sample_trace import TraceTuple
-        n_call = None
         if isinstance(x_p, TraceTuple):
             dev = self._run_on_device(x_p, logp, logp_p)
             if dev is not None:
                 return dev
-            n_call, x_p = x_p.n_call, x_p.get(flatten=False)
-        else:
-            try:
-                x_p = np.asarray(x_p, dtype=np.float64)
-            except Exception:
-                x_p = None
-            if x_p is None or x_p.ndim not in (2, 3):
-                raise ValueError('invalid value for x_p.')
-        n_samples = int(np.prod(x_p.shape[:-1]))
-        if x_p.shape[-1] < 2 or n_samples < 2:
-            raise ValueError('invalid shape for x_p.')
-        n_q = self._draws_from_q(n_samples, n_call)
-        if x_p.shape[0] == 1:   # a single chain: drop the chain axis, the halves are then halves of the iterations
-            x_p = x_p[0]
+        n_call, x_p = _host_samples(x_p)
+        n_samples, x_p = _checked_shape(x_p)
+        n_q = _draws_from_q(self.n_q, self.f_call, n_samples, n_call)
         cut = x_p.shape[0] // 2
         train, test = x_p[:cut], x_p[cut:]
         self.sit.fit(data=train)
@@ -108,7 +152,7 @@ class GBS:
             if known.shape == x_p.shape[:-1]:
                 known = known[cut:]
             else:
-                warnings.warn('the logp_p you gave me seems not correct. Will recompute it from logp and x_p.', RuntimeWarning)
+                warnings.warn(_WRONG_LOGP_P, RuntimeWarning)
                 known = None
         if known is None:
             known = _evaluate(logp, test)
@@ -119,30 +163,15 @@ class GBS:
         a SIT with the default generator and ``logp`` the ``logp`` method of a ``SurrogateDensity`` (whose kernel takes device
         tensors).  The halves, the SIT's draws and the four log-density vectors stay on the GPU; only the vectors (n,) visit the
         host, for ``bridge``.  None when any of that does not hold (the host path runs)."""
-        import torch
-        from ..core.density import SurrogateDensity
         from ..utils import sobol
-        from .. import parallel
-        if type(logp) is SurrogateDensity:
-            den = logp
-        else:
-            den = getattr(logp, '__self__', None)
-            if not (isinstance(den, SurrogateDensity) and getattr(logp, '__func__', None) in (SurrogateDensity.logp, SurrogateDensity.__call__)):
-                return None
-        if self.sit.mvn_generator is not sobol.multivariate_normal or parallel.world()[1] > 1:
+        den = _device_density(logp)
+        if den is None or self.sit.mvn_generator is not sobol.multivariate_normal:
             return None
-        t = trace.device('samples_original')
-        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+        x_p = _device_samples(trace)   # (None for more than one rank, or a trace without a device tensor)
+        if x_p is None:
             return None
-        x_p = t[:, trace.n_warmup:]                       # TraceTuple.get(flatten=False): (chain, iteration, d) after the warm-up
-        if trace.n_warmup >= trace.i_iter - 1:
-            raise ValueError('since_iter is too large. Nothing to return.')
-        n_samples = int(x_p.shape[0] * x_p.shape[1])
-        if x_p.shape[-1] < 2 or n_samples < 2:
-            raise ValueError('invalid shape for x_p.')
-        n_q = self._draws_from_q(n_samples, trace.n_call)
-        if x_p.shape[0] == 1:
-            x_p = x_p[0]
+        n_samples, x_p = _checked_shape(x_p)
+        n_q = _draws_from_q(self.n_q, self.f_call, n_samples, trace.n_call)
         cut = x_p.shape[0] // 2
         d = x_p.shape[-1]
         train, test = x_p[:cut].reshape(-1, d), x_p[cut:].reshape(-1, d).contiguous()
@@ -155,7 +184,7 @@ class GBS:
             if known.shape == tuple(x_p.shape[:-1]):
                 known = known[cut:]
             else:
-                warnings.warn('the logp_p you gave me seems not correct. Will recompute it from logp and x_p.', RuntimeWarning)
+                warnings.warn(_WRONG_LOGP_P, RuntimeWarning)
                 known = None
         if known is None:
             known = dd.logp_and_grad(test, True)[0].cpu().numpy().reshape(tuple(x_p.shape[:-1])[0] - cut, *x_p.shape[1:-1])

@@ -312,28 +312,42 @@ class _DeviceBackend:
         return bits.view(np.float64), _DeviceSeries(self, series.buf)
 
 
-def _device_batches(x, clock):
+def _device_batches(x, n_rows):
+    """The batches of at most 16 parameters of x (n_chain, n_t, n_d), each as (tensor the column kernels read, first column in
+    it, number of columns); ``n_rows`` values per parameter go through the kernels.  They read float64 or float32 with unit stride
+    along n_d in place; anything else is converted batch by batch (one more batch-sized buffer, never a copy of the whole tensor).
+    The size limit is checked at the call, before the caller allocates anything; the batches come from the generator returned."""
+    import torch
+    from .. import _lib
+    if n_rows > 2**31 - 1:
+        raise NotImplementedError('more than 2^31 - 1 values per parameter.')
+    in_place = x.dtype in (torch.float64, torch.float32) and (x.shape[2] == 1 or x.stride(2) == 1)
+    n_d, w = int(x.shape[2]), _lib.DIAG_BATCH
+
+    def batches():
+        for k0 in range(0, n_d, w):
+            nb = min(w, n_d - k0)
+            if in_place:
+                yield x, k0, nb
+            else:
+                yield x[:, :, k0:k0 + nb].to(torch.float64).contiguous(), 0, nb
+    return batches()
+
+
+def _device_backends(x, clock):
     import torch
     from .. import _lib
     from ..device import get_context
-    # the column kernel reads float64 or float32 with unit stride along n_d in place; anything else is converted batch by batch
-    # (one more batch-sized buffer, never a copy of the whole tensor)
-    in_place = x.dtype in (torch.float64, torch.float32) and (x.shape[2] == 1 or x.stride(2) == 1)
-    big_m, n_t, n_d = (int(v) for v in x.shape)
+    big_m, n_t = int(x.shape[0]), int(x.shape[1])
     h = n_t // 2
     s = 2 * big_m * h
-    if s > 2**31 - 1:
-        raise NotImplementedError('more than 2^31 - 1 values per parameter.')
+    batches = _device_batches(x, s)
     ctx = get_context(x.device.index)
-    w = _lib.DIAG_BATCH
-    shared = dict(ctx=ctx, buf=ctx.empty((2 * big_m, h, w)), keys=ctx.empty((s,), dtype=torch.int64),
-                  order=ctx.empty((s,), dtype=torch.int32), ones=torch.ones((2 * big_m, w), dtype=torch.float64, device=x.device))
-    for k0 in range(0, n_d, w):
-        nb = min(w, n_d - k0)
-        if in_place:
-            yield _DeviceBackend(x, n_t & 1, h, k0, nb, shared, clock)
-        else:
-            yield _DeviceBackend(x[:, :, k0:k0 + nb].to(torch.float64).contiguous(), n_t & 1, h, 0, nb, shared, clock)
+    shared = dict(ctx=ctx, buf=ctx.empty((2 * big_m, h, _lib.DIAG_BATCH)), keys=ctx.empty((s,), dtype=torch.int64),
+                  order=ctx.empty((s,), dtype=torch.int32),
+                  ones=torch.ones((2 * big_m, _lib.DIAG_BATCH), dtype=torch.float64, device=x.device))
+    for xb, k0, nb in batches:
+        yield _DeviceBackend(xb, n_t & 1, h, k0, nb, shared, clock)
 
 
 def _host_batches(x):
@@ -357,7 +371,7 @@ def _compute(x, want, probs=(), prob=(0.05, 0.95), stats=None):
     if getattr(x, 'is_cuda', False):
         import torch
         with torch.cuda.device(x.device):
-            parts = [_batch(be, want, probs, prob) for be in _device_batches(x, _Clock(stats, torch))]
+            parts = [_batch(be, want, probs, prob) for be in _device_backends(x, _Clock(stats, torch))]
     else:
         parts = [_batch(be, want, probs, prob) for be in _host_batches(x)]
     return {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]}

@@ -44,7 +44,7 @@ whatever n_d is.  Every device reduction has a fixed order, so the same input gi
 a parameter lands in.  At most 2^31 - 1 values."""
 import numpy as np
 
-from .diagnostics import Summary, _check_probs, _lerp
+from .diagnostics import Summary, _check_probs, _device_batches, _lerp
 
 __all__ = ['psis', 'PSISResult', 'weighted_summary']
 
@@ -224,11 +224,9 @@ def _device_table(x, w, probs):
     import torch
     from .. import _lib
     from ..device import get_context, _ptr
-    n_chain, n_draw, n_d = (int(v) for v in x.shape)
+    n_chain, n_draw = int(x.shape[0]), int(x.shape[1])
     n = n_chain * n_draw
-    if n > 2**31 - 1:
-        raise NotImplementedError('more than 2^31 - 1 values per parameter.')
-    in_place = x.dtype in (torch.float64, torch.float32) and (n_d == 1 or x.stride(2) == 1)
+    batches = _device_batches(x, n)
     with torch.cuda.device(x.device):
         ctx = get_context(x.device.index)
         lib, h, width = ctx._lib, ctx.handle, _lib.DIAG_BATCH
@@ -241,10 +239,7 @@ def _device_table(x, w, probs):
         keys, order = ctx.empty((n,), dtype=torch.int64), ctx.empty((n,), dtype=torch.int32)
         probs_d = torch.as_tensor(probs, device=x.device)
         parts = []
-        for k0 in range(0, n_d, width):
-            nb = min(width, n_d - k0)
-            # (input the column kernel cannot read in place is converted a batch at a time, as in diagnostics._device_batches)
-            xb, kb = (x, k0) if in_place else (x[:, :, k0:k0 + nb].to(torch.float64).contiguous(), 0)
+        for xb, kb, nb in batches:
             out, qout = ctx.empty((5, width)), ctx.empty((len(probs), width))
             _lib.check(lib.bfhip_wstat_columns(h, n_chain, n_draw, int(xb.stride(0)), int(xb.stride(1)), _ptr(xb),
                                                int(xb.dtype == torch.float32), 0, kb, nb, _ptr(w), _ptr(buf)))

@@ -596,7 +596,7 @@ def test_importance_weights_match_np_exp_and_np_clip():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('n', [5, 257, 65537, 200003])
+@pytest.mark.parametrize('n', [5, 255, 256, 257, 65537, 200003])
 def test_importance_weights_special_values_follow_the_host_route(n):
     """logp = -inf is a zero weight; +inf an infinite one (so an infinite cap); one NaN makes the cap NaN, so np.clip --
     the host route and the reference -- makes every truncated weight NaN, and so must the kernel."""

@@ -35,7 +35,7 @@ if os.path.join(HERE, 'helpers') not in sys.path:
 import psis_reference as pr  # noqa: E402
 
 RTOL = 1e-9
-SIZES = (24, 25, 224, 225, 226, 257, 1000, 4097, 100003, 262145)
+SIZES = (1, 24, 25, 224, 225, 226, 255, 256, 257, 1000, 4097, 100003, 262145)
 TABLE_SHAPES = [(1, 3), (2, 2), (255, 1), (256, 17), (257, 16), (7, 333, 5), (65537, 2)]
 
 
