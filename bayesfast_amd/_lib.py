@@ -128,6 +128,12 @@ SYMBOLS = {
     'bfhip_wstat_moments': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
     'bfhip_wstat_cumweights': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp]),
     'bfhip_wstat_quantiles': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp]),
+    'bfhip_marg_quantise': (C.c_int, [_vp, C.c_long, _vp, C.c_int, _vp, _vp]),
+    'bfhip_marg_extent': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
+    'bfhip_marg_hist1d': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    'bfhip_marg_index': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_long, C.c_int]),
+    'bfhip_marg_hist2d': (C.c_int, [_vp, C.c_long, _vp, C.c_long, _vp, C.c_long, _vp, C.c_int, _vp]),
+    'bfhip_marg_levels': (C.c_int, [_vp, C.c_long, C.c_long, _vp, C.c_int, _vp, _vp, _vp]),
     'bfhip_logp_hess': (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     'bfhip_laplace_opt': (C.c_int, [_vp, C.POINTER(LaplaceOpts), C.c_int, _vp, _vp, _vp, _vp, _vp]),
     'bfhip_pipeline_logp_hess': (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
@@ -141,6 +147,8 @@ WSUM_FORMS = {'built': 0, 'packed': 1, 'unpacked': 2}   # BFHIP_WSUM_BUILT / _PA
 ACOR_MAX_GROUPS = 256   # walker groups of bfhip_acor_lag_sums: its work buffer is min(n_w, 256) * n_lag * n_d doubles
 DIAG_BATCH = 16         # BFHIP_DIAG_BATCH: parameters per batch of the bfhip_diag_* passes (the width of their series buffers)
 WSTAT_WORK = 65536      # BFHIP_WSTAT_WORK: doubles of bfhip_wstat_moments' work buffer
+MARG_MAX_BINS, MARG_MAX_BINS2D, MARG_MAX_LD = 1024, 128, 256   # BFHIP_MARG_MAX_BINS / _BINS2D / _LD
+MARG_EXTENT_WORK = 32768   # BFHIP_MARG_EXTENT_WORK: doubles of bfhip_marg_extent's work buffer
 WSTAT_TILE = 2048       # sorted positions per workgroup of bfhip_wstat_cumweights: its work buffer is ceil(n / 2048) doubles
 
 

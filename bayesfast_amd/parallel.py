@@ -7,7 +7,7 @@ chain index, so results do not depend on the number of ranks.  The refit needs e
 ONE all-gather per sampling round (RCCL over xGMI with backend "nccl"; gloo in the CPU tests)."""
 import numpy as np
 
-__all__ = ['world', 'shard_range', 'all_gather_chains', 'local_device', 'broadcast_int', 'all_reduce_sum', 'all_gather_stack']
+__all__ = ['world', 'shard_range', 'all_gather_chains', 'local_device', 'broadcast_int', 'all_reduce_sum', 'all_reduce_max', 'all_gather_stack']
 
 
 def world():
@@ -77,18 +77,28 @@ def broadcast_int(v, src=0):
     return int(t.item())
 
 
-def all_reduce_sum(t):
-    """Sum of a tensor over the ranks, in place (a no-op without a process group)."""
+def _all_reduce(t, op):
     rank, ws = world()
     if ws > 1:
         import torch.distributed as dist
         if dist.get_backend() == 'gloo' and t.is_cuda:  # (plumbing tests: gloo moves host tensors)
             h = t.cpu()
-            dist.all_reduce(h, op=dist.ReduceOp.SUM)
+            dist.all_reduce(h, op=getattr(dist.ReduceOp, op))
             t.copy_(h)
         else:
-            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            dist.all_reduce(t, op=getattr(dist.ReduceOp, op))
     return t
+
+
+def all_reduce_sum(t):
+    """Sum of a tensor over the ranks, in place (a no-op without a process group)."""
+    return _all_reduce(t, 'SUM')
+
+
+def all_reduce_max(t):
+    """Elementwise maximum of a tensor over the ranks, in place (a no-op without a process group).  The tensor should hold no NaN:
+    which operand a maximum keeps then depends on the backend."""
+    return _all_reduce(t, 'MAX')
 
 
 def all_gather_stack(t):

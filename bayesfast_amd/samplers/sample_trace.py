@@ -475,6 +475,38 @@ class TraceTuple:
         return weighted_summary(self._diag_input(since_iter, include_warmup, original_space, return_type), log_weights=log_weights,
                                 probs=probs)
 
+    def _local_samples(self, since_iter, include_warmup, original_space):
+        """This rank's chains of what ``get(..., flatten=False)`` selects, as a view of the parts (n_chain_local, n_t, n_d),
+        unmaterialised; unlike ``_diag_input`` with any number of ranks: for the statistics that are collectives."""
+        if since_iter is None:
+            since_iter = 0 if include_warmup else self.n_warmup
+        since_iter = int(since_iter)
+        if since_iter >= self.i_iter - 1:
+            raise ValueError('since_iter is too large. Nothing to return.')
+        return self._parts['samples_original' if original_space else 'samples'][:, since_iter:]
+
+    def marginals(self, log_weights=None, since_iter=None, include_warmup=False, original_space=True, **options):
+        """The marginal posterior histograms and credible levels (``bayesfast_amd.utils.marginals``: a ``Marginals``) of the draws
+        that ``get(since_iter, include_warmup, original_space, flatten=False)`` selects, read where ``sample()`` left them;
+        ``options`` are ``bins``, ``bins2d``, ``ranges``, ``params``, ``pairs`` and ``probs``.  ``log_weights``, if given, holds one
+        log weight per selected draw of THIS rank, shaped (n_chain_local, n_t) or flat in that order.  Under ``torch.distributed``
+        with more than one rank a collective, to be called by every rank: every rank gets the same result, identical bin for bin
+        to one process over all chains, and only the weights' maximum, the draw count, the extremes and the int64 bins cross
+        between ranks (no ``gather()``)."""
+        from ..utils.marginals import _weights_of, _check_options, _make_passes, marginals_sharded
+        x = self._local_samples(since_iter, include_warmup, original_space)
+        unknown = set(options) - {'bins', 'bins2d', 'ranges', 'params', 'pairs', 'probs'}
+        if unknown:
+            raise TypeError('unexpected options: %s.' % ', '.join(sorted(unknown)))
+        opt = dict(bins=64, bins2d=64, ranges=None, params=None, pairs='all', probs=(0.68, 0.95))
+        opt.update(options)
+        d_all = int(x.shape[-1])
+        given, kind = _weights_of(tuple(x.shape), log_weights, None)
+        checked = _check_options(d_all, **opt)
+        if getattr(x, 'is_cuda', False) and len(checked[4]) and len(checked[3]) > _lib.MARG_MAX_LD:
+            raise NotImplementedError('pairs of more than %d parameters on the device route.' % _lib.MARG_MAX_LD)
+        return marginals_sharded(_make_passes(x, given, kind, checked[3], d_all), *checked)
+
     def __getitem__(self, key):
         return self.sample_traces[key]
 

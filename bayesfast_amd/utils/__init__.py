@@ -2,7 +2,8 @@ from .acor import integrated_time, AutocorrError
 from .resample import SystematicResampler
 from .diagnostics import rhat, ess, summary
 from .psis import psis, PSISResult, weighted_summary
+from .marginals import marginals, Marginals
 from .laplace import Laplace, LaplaceResult, make_positive
 
 __all__ = ['SystematicResampler', 'integrated_time', 'AutocorrError', 'Laplace', 'LaplaceResult', 'make_positive', 'rhat', 'ess', 'summary',
-           'psis', 'PSISResult', 'weighted_summary']
+           'psis', 'PSISResult', 'weighted_summary', 'marginals', 'Marginals']

@@ -69,6 +69,9 @@ def main():
         r.log_mean_weight))
     print('weighted posterior of the first 4 parameters:')
     print(weighted_summary(xs[:, :4], log_weights=r.log_weights))
+    from bayesfast_amd.utils import marginals
+    m = marginals(xs[:, :4], log_weights=r.log_weights, probs=(0.68,))
+    print('68 %% highest-density region of parameter 0 from its weighted histogram:', m.interval(0, 0.68))
 
 
 if __name__ == '__main__':

@@ -37,7 +37,8 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_DIM 128         /* input_size limit of the device path */
 #define BFHIP_MAX_TREEDEPTH 12
 
-/* 108: bfhip_wave_packs_probe; bfhip_psis and bfhip_wstat_columns / _moments / _cumweights / _quantiles, the Pareto-smoothed importance
+/* 108: bfhip_marg_quantise / _extent / _hist1d / _index / _hist2d / _levels, the marginal posterior histograms and their credible levels
+ * (additions only: the number stays).  bfhip_wave_packs_probe; bfhip_psis and bfhip_wstat_columns / _moments / _cumweights / _quantiles, the Pareto-smoothed importance
  * weights and the weighted posterior table (additions only: the number stays).
  * 107: bfhip_pipeline_logp_hess and bfhip_pipeline_laplace_opt, the analytic and the Gauss-Newton Hessian of the pipeline density and
  * its device Newton maximiser.  106: bfhip_wave_sum_probe.
@@ -570,6 +571,46 @@ int bfhip_wstat_moments(bfhip_ctx *ctx, long n, const double *series, const doub
 int bfhip_wstat_cumweights(bfhip_ctx *ctx, long n, const uint32_t *order, const double *w, double *cum, double *work);
 int bfhip_wstat_quantiles(bfhip_ctx *ctx, long n, const uint64_t *keys_sorted, const uint32_t *order, const double *w, const double *cum,
                           const double *wsum, int nq, const double *probs, int b, double *out);
+
+/* Marginal posterior histograms and credible levels of (weighted) draws (bayesfast_amd/utils/marginals.py has the definitions), on a
+ * batch of at most BFHIP_DIAG_BATCH parameters in a (n, BFHIP_DIAG_BATCH) series buffer as bfhip_wstat_columns writes it with w = NULL.
+ * Everything that is accumulated is a 64-bit integer: the weights are fixed-point numbers q, a histogram is a sum of q's, and integer
+ * sums do not depend on their order -- LDS and global atomics, any launch shape, any sharding of the rows give the same bits.
+ *   bfhip_marg_quantise  q[i] = floor(wp[i] 2^k) as uint64 for normalised weights wp (n,) in [0, 1] and 0 <= k <= 62 (2^k wp is exact);
+ *                        wp NULL: q[i] = 1.  A weight that is negative, NaN or above 1 gets q = 0 and ADDS one to *flag (the caller
+ *                        zeroes it).  With k = 62 - ceil(log2 n_all) the sum of the q of n_all draws is at most 2^62.
+ *   bfhip_marg_extent    lo, hi (BFHIP_DIAG_BATCH,) <- per column the smallest and the largest FINITE value among the rows with q > 0
+ *                        (q NULL: every row); +inf and -inf for a column without one.  work: BFHIP_MARG_EXTENT_WORK doubles.
+ *   bfhip_marg_hist1d    for the columns b < nb and device doubles lo, hi, inv (BFHIP_DIAG_BATCH,): a finite value with lo <= x <= hi
+ *                        goes to bin min(floor((x - lo) inv), n_bins - 1) -- a subtraction, then a multiplication -- anything else to
+ *                        outside[b][0 .. 2]: below, above, not finite.  hist (BFHIP_DIAG_BATCH, n_bins) and outside (BFHIP_DIAG_BATCH, 3),
+ *                        uint64, are ADDED to, in units of q; rows with q = 0 are not read.  1 <= n_bins <= BFHIP_MARG_MAX_BINS.
+ *   bfhip_marg_index     idx[r ld + col0 + b] <- the same bin as one uint8, 255 for "not in range", b < nb, 1 <= n_bins <=
+ *                        BFHIP_MARG_MAX_BINS2D; idx is a (n, ld) byte matrix, ld >= col0 + nb.
+ *   bfhip_marg_hist2d    hist[p][idx[r][pairs[p][0]]][idx[r][pairs[p][1]]] += q[r] (q NULL: 1) over the rows where both indices are
+ *                        below n_bins; pairs (n_pair, 2) int32 on the device (repeats and (i, i) allowed; a column outside [0, ld) adds
+ *                        nothing), hist (n_pair, n_bins, n_bins) uint64, ADDED to.  idx 16-byte aligned, ld a power of two from 16 to
+ *                        BFHIP_MARG_MAX_LD.  A workgroup keeps the histograms of a group of pairs in LDS as uint64 (4 pairs at 64 x 64,
+ *                        one at 128 x 128 of the CU's 160 KB), reads a tile of index rows once for all of them, adds with 64-bit LDS
+ *                        atomics and flushes its non-zero bins with 64-bit global atomics.
+ *   bfhip_marg_levels    a workgroup per histogram of n_hist contiguous ones of m <= 16384 uint64 bins: total[h] <- S = the sum, and
+ *                        levels[h n_p + i] <- the largest bin value v with (double)(sum of the bins >= v) >= probs[i] (double)S
+ *                        (probs: n_p device doubles in (0, 1]); 0 for an empty histogram.  Exact: at most 64 integer counts.
+ * Stream-ordered, no host synchronisation; 64-bit offsets, n <= 2^31 - 1. */
+#define BFHIP_MARG_MAX_BINS 1024
+#define BFHIP_MARG_MAX_BINS2D 128
+#define BFHIP_MARG_MAX_LD 256
+#define BFHIP_MARG_EXTENT_WORK 32768
+int bfhip_marg_quantise(bfhip_ctx *ctx, long n, const double *wp, int k, uint64_t *q, uint64_t *flag);
+int bfhip_marg_extent(bfhip_ctx *ctx, long n, const double *series, const uint64_t *q, double *lo, double *hi, double *work);
+int bfhip_marg_hist1d(bfhip_ctx *ctx, long n, const double *series, const uint64_t *q, const double *lo, const double *hi,
+                      const double *inv, int nb, int n_bins, uint64_t *hist, uint64_t *outside);
+int bfhip_marg_index(bfhip_ctx *ctx, long n, const double *series, const double *lo, const double *hi, const double *inv, int nb,
+                     int n_bins, uint8_t *idx, long ld, int col0);
+int bfhip_marg_hist2d(bfhip_ctx *ctx, long n, const uint8_t *idx, long ld, const int32_t *pairs, long n_pair, const uint64_t *q,
+                      int n_bins, uint64_t *hist);
+int bfhip_marg_levels(bfhip_ctx *ctx, long n_hist, long m, const uint64_t *hist, int n_p, const double *probs, uint64_t *levels,
+                      uint64_t *total);
 
 /* The OptimizeStep's Laplace approximation (utils/laplace.py:131-183; the reference differences the gradient with numdifftools, at
  * every Newton-CG iteration and once more at the maximum, one point per call).  Both calls take the uploaded SCALAR surrogate density
