@@ -7,33 +7,7 @@
 // G^T = M . X^T maps the layout onto itself, so a matvec needs no data movement at all.
 #pragma once
 #include "bfhip_common.h"
-
-// constraint transform of one coordinate: transforms/_constraint.pyx:133-215 (to_original f, j, jj)
-__device__ inline void bf_to_original(double x, int kind, double lo, double rg, double &xo, double &J, double &J2) {
-    double tmp, jt, j2t;
-    if (kind == 1) {
-        tmp = 1. / (1. + exp(-x));
-        jt = tmp * (1. - tmp);
-        double t2 = exp(x);
-        j2t = -t2 * (t2 - 1.) / (t2 + 1.) / (t2 + 1.) / (t2 + 1.);
-    } else if (kind == 2) {
-        tmp = exp(x);
-        jt = tmp;
-        j2t = tmp;
-    } else if (kind == 3) {
-        double ex = exp(x);
-        tmp = 1. - ex;
-        jt = -ex;
-        j2t = -ex;
-    } else {
-        tmp = x;
-        jt = 1.;
-        j2t = 0.;
-    }
-    xo = lo + tmp * rg;
-    J = jt * rg;
-    J2 = j2t * rg;
-}
+#include "bfhip_constraint.h"
 
 // Cubic-2 and cubic-3 contributions to gradient component `dim` of one point (modules/_poly.pyx:49-137),
 // compact masked tables (DevModel).  X(k) returns x_k of the point; xj = x_dim.
@@ -127,11 +101,10 @@ __device__ inline void bf_eval_w1(const DevModel &mm, const double *Sf, const do
         jac[e] = 1.;
         gj[e] = 0.;
         if (tr) {
-            double J, J2;
-            bf_to_original(x[e], (int)pd[PD_KIND * DP + dim], pd[PD_LO * DP + dim], pd[PD_RG * DP + dim], xo, J, J2);
-            logdet += log(fabs(J));
+            double J, lj;
+            bf_to_original(x[e], (int)pd[PD_KIND * DP + dim], pd[PD_LO * DP + dim], pd[PD_RG * DP + dim], xo, J, lj, gj[e]);
+            logdet += lj;
             jac[e] = J;
-            gj[e] = J2 / J;
         }
         hv[e] = xo;  // keep xo for the decay term
         xs[e] = m.has_su ? (xo - pd[PD_SU_LO * DP + dim]) / pd[PD_SU_DIFF * DP + dim] : xo;

@@ -491,9 +491,8 @@ __global__ void bf_constraint_kernel(DevModel m, int which, long total, const do
     const double lo = m.pd[PD_LO * m.DP + i], rg = m.pd[PD_RG * m.DP + i];
     double r;
     if (which >= 3) {
-        double xo, J, J2;
-        bf_to_original(xv, kind, lo, rg, xo, J, J2);
-        r = which == 3 ? xo : (which == 4 ? J : J2);
+        const BfConstraint tc = bf_constraint(xv, kind, lo, rg);
+        r = which == 3 ? tc.xo : (which == 4 ? tc.J : tc.gj * tc.J);   // (jj = T'' = (T'' / T') T')
     } else {
         double t = (xv - lo) / rg;
         const bool oob = (kind == 1 && (t <= 0. || t >= 1.)) || (kind == 2 && t <= 0.) || (kind == 3 && t >= 1.);

@@ -44,6 +44,7 @@
 // P1 | F = C' Phi | P2 | W = C'^T r | P3 | gradient gather, second half step, U-turn sums | B3 | the state machine as before.
 #pragma once
 #include "bfhip_lane.h"
+#include "bfhip_constraint.h"
 #include "bfhip_sampler_defs.h"
 #include "bfhip_oob.h"
 #include "bfhip_pld.h"
@@ -108,22 +109,14 @@ struct GroupGeo {
     static constexpr int scratch_slots() { return S_DEEP + (NDEEP * W + DP - 1) / DP; }
 };
 
-// Constraint transform of one coordinate, transforms/_constraint.pyx:133-215: the original coordinate xo, the Jacobian J and
-// the ratio J2 / J the gradient needs (density.py:749-750).  One exponential serves every kind (lanes of a wave hold
-// coordinates of different kinds, so branches would run all of them): with e = exp(-x) the logistic kind is
-// t = 1 / (1 + e), J = t (1 - t) rg and J2 / J = -t2 (t2 - 1) / (t2 + 1)^3 / (t (1 - t)) = (e - 1) t  (t2 = exp(x) = 1 / e);
-// the one-sided kinds have J2 = J.  Agrees with the statement-by-statement form (bf_to_original, bfhip_eval.h) to rounding.
-BF_DEV void bf_to_original_g(double x, int kind, double lo, double rg, double &xo, double &J, double &gj) {
-    const double e = bf_exp(kind == 1 ? -x : x);
-    const double t = 1. / (1. + e);
-    double tmp = x, jt = 1., gq_ = 0.;
-    if (kind == 1) { tmp = t; jt = t * (1. - t); gq_ = (e - 1.) * t; }
-    if (kind == 2) { tmp = e; jt = e; gq_ = 1.; }
-    if (kind == 3) { tmp = 1. - e; jt = -e; gq_ = 1.; }
-    xo = lo + tmp * rg;
-    J = jt * rg;
-    gj = gq_;
-}
+// exp for the constraint transform (bfhip_constraint.h): the emulated build's bf_exp on the host
+struct BfLaneExp {
+#ifdef BF_HOST_EMU
+    double operator()(double x) const { return bf_exp(x); }
+#else
+    __device__ __forceinline__ double operator()(double x) const { return bf_exp(x); }
+#endif
+};
 
 template <int W, bool NUTS, int FS>
 BF_DEV void bf_group_body(const DevModel &m, const SamplerArgs &a, double *lds) {
@@ -432,7 +425,7 @@ BF_DEV void bf_group_body(const DevModel &m, const SamplerArgs &a, double *lds) 
         // ================= phase A: first half of the leapfrog step, B operands =================
         const bool ev = mode != M_DONE;
         double xs[4], xev[4], jac[4], gj[4], xo[4];
-        double ldet[4] = {0., 0., 0., 0.};
+        double ldet[4] = {0., 0., 0., 0.}, llin[4] = {0., 0., 0., 0.};   // log|J_r| = llin[r] + log(ldet[r]) (bfhip_constraint.h)
         if (ev) {
             eps_t = (mode == M_LEAF) ? eps * (double)dir : 0.;  // compute_state (base_hmc.py:70) is a step of length 0
             const double dt = 0.5 * eps_t;
@@ -449,11 +442,12 @@ BF_DEV void bf_group_body(const DevModel &m, const SamplerArgs &a, double *lds) 
             gj[r] = 0.;
             if constexpr (TR) {
                 if (ev) {
-                    double J, g2;
-                    bf_to_original_g(q[r], c_kind[r], c_lo[r], c_rg[r], xs[r], J, g2);
-                    ldet[r] = bf_fabs(J);  // (|dx/dx_t| of this coordinate; its logarithm is taken below, once per lane)
-                    jac[r] = J;
-                    gj[r] = g2;
+                    const BfConstraint tc = bf_constraint<false>(q[r], c_kind[r], c_lo[r], c_rg[r], BfLaneExp());
+                    xs[r] = tc.xo;
+                    llin[r] = tc.lin;
+                    ldet[r] = tc.c;  // (the factor of |dx/dx_t| that is not a power of e; its logarithm is taken below, once per lane)
+                    jac[r] = tc.J;
+                    gj[r] = tc.gj;
                 }
             }
             xo[r] = xs[r];
@@ -571,10 +565,10 @@ BF_DEV void bf_group_body(const DevModel &m, const SamplerArgs &a, double *lds) 
                 if (bf_any(ev && !(pj > 1e-280 && pj < 1e280))) {
                     double l4[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) l4[r] = ev ? bf_log(ldet[r]) : 0.;
+                    for (int r = 0; r < 4; ++r) l4[r] = ev ? llin[r] + bf_log(ldet[r]) : 0.;
                     lsum = sum4(l4);
                 } else {
-                    lsum = ev ? bf_log(pj) : 0.;
+                    lsum = ev ? sum4(llin) + bf_log(pj) : 0.;
                 }
                 post(G::V_LOGDET, lsum);
             }
@@ -618,18 +612,19 @@ BF_DEV void bf_group_body(const DevModel &m, const SamplerArgs &a, double *lds) 
             }
             if constexpr (DEC) post(G::V_BD2, sum4(t_bd2));
             if constexpr (TR) {
-                // sum_r log|J_r| (density.py:748) as the logarithm of the lane's product: one log instead of four.  The
-                // product of four Jacobians stays far from underflow unless a coordinate sits ~700 logistic units deep
-                // in a bound's tail; then (any lane of the wave) the four logarithms are taken one by one.
+                // sum_r log|J_r| (density.py:748): the linear parts, and ONE logarithm of the lane's product of the four
+                // factors c_r.  A factor is of the size of its range (this kernel leaves the helper's J == 0 test out), so the
+                // product leaves [1e-280, 1e280] only for extreme ranges; then (any lane of the wave) the four logarithms
+                // are taken one by one.
                 double pj = (ldet[0] * ldet[1]) * (ldet[2] * ldet[3]);
                 double lsum;
                 if (bf_any(ev && !(pj > 1e-280 && pj < 1e280))) {
                     double l4[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) l4[r] = ev ? bf_log(ldet[r]) : 0.;
+                    for (int r = 0; r < 4; ++r) l4[r] = ev ? llin[r] + bf_log(ldet[r]) : 0.;
                     lsum = sum4(l4);
                 } else {
-                    lsum = ev ? bf_log(pj) : 0.;
+                    lsum = ev ? sum4(llin) + bf_log(pj) : 0.;
                 }
                 post(G::V_LOGDET, lsum);
             }

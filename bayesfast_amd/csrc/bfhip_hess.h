@@ -24,6 +24,7 @@
 #pragma once
 #include <math.h>
 #include "bfhip_model.h"
+#include "bfhip_constraint.h"
 
 #ifdef BF_HOST_EMU
 #define BF_HESS_SYNC() ((void)0)
@@ -81,33 +82,17 @@ struct BfHessPt {
     double dphi, prec;
 };
 
-// constraint transform of one coordinate with the derivatives the Hessian needs (transforms/_constraint.pyx:133-215)
-__host__ __device__ inline void bf_hess_transform(double x, int kind, double lo, double rg, double &xo, double &J, double &J2, double &lj2) {
-    double tmp, jt, j2t;
-    lj2 = 0.;
-    if (kind == 1) {
-        tmp = 1. / (1. + exp(-x));
-        jt = tmp * (1. - tmp);
-        double t2 = exp(x);
-        j2t = -t2 * (t2 - 1.) / (t2 + 1.) / (t2 + 1.) / (t2 + 1.);
-        lj2 = -2. * jt;   // log T' = log s + log(1 - s) + const
-    } else if (kind == 2) {
-        tmp = exp(x);
-        jt = tmp;
-        j2t = tmp;
-    } else if (kind == 3) {
-        double ex = exp(x);
-        tmp = 1. - ex;
-        jt = -ex;
-        j2t = -ex;
-    } else {
-        tmp = x;
-        jt = 1.;
-        j2t = 0.;
-    }
-    xo = lo + tmp * rg;
-    J = jt * rg;
-    J2 = j2t * rg;
+// constraint transform of one coordinate with the derivatives the Hessian needs (bfhip_constraint.h): T, T', T'', log|T'| and
+// the first two derivatives of log|T'|
+__host__ __device__ inline void bf_hess_transform(double x, int kind, double lo, double rg, double &xo, double &J, double &J2, double &lj,
+                                                  double &gj, double &lj2) {
+    const BfConstraint tc = bf_constraint(x, kind, lo, rg);
+    xo = tc.xo;
+    J = tc.J;
+    J2 = tc.gj * tc.J;
+    lj = tc.lin + log(tc.c);
+    gj = tc.gj;
+    lj2 = bf_constraint_lj2(tc, kind);
 }
 
 // cubic-2 and cubic-3 contributions to gradient component i at the point x (modules/_poly.pyx:49-137; bf_cubic_grad of bfhip_eval.h)
@@ -180,17 +165,17 @@ __host__ __device__ inline BfHessPt bf_hess_eval(const DevModel &m, const double
     r.prec = 0.;
     BF_HESS_SYNC();   // the previous evaluation's readers are done
     for (int i = tid; i < d; i += nt) {
-        double xo = x[i], J = 1., J2 = 0., lj2 = 0.;
-        if (r.tr) bf_hess_transform(x[i], (int)pd[PD_KIND * DP + i], pd[PD_LO * DP + i], pd[PD_RG * DP + i], xo, J, J2, lj2);
+        double xo = x[i], J = 1., J2 = 0., lj = 0., gj = 0., lj2 = 0.;
+        if (r.tr) bf_hess_transform(x[i], (int)pd[PD_KIND * DP + i], pd[PD_LO * DP + i], pd[PD_RG * DP + i], xo, J, J2, lj, gj, lj2);
         const double diff = m.has_su ? pd[PD_SU_DIFF * DP + i] : 1.;
         w.xo[i] = xo;
         w.xs[i] = m.has_su ? (xo - pd[PD_SU_LO * DP + i]) / diff : xo;
         w.J[i] = J;
         w.a[i] = J / diff;
         w.b[i] = J2 / diff;
-        w.lj[i] = r.tr ? log(fabs(J)) : 0.;
+        w.lj[i] = lj;
         w.lj2[i] = lj2;
-        w.gj[i] = r.tr ? J2 / J : 0.;
+        w.gj[i] = gj;
     }
     BF_HESS_SYNC();
     for (int i = tid; i < d; i += nt) {

@@ -272,11 +272,11 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
                 }
                 xs = q;
                 if constexpr (TR) {
-                    double J, J2;
-                    bf_to_original(q, c_kind, c_lo, c_rg, xs, J, J2);
-                    logdet_l = 0. + LN_LOGV(fabs(J));
-                    jac = J;
-                    gj = J2 / J;
+                    const BfConstraint tc = bf_constraint<false>(q, c_kind, c_lo, c_rg);
+                    xs = tc.xo;
+                    logdet_l = tc.lin + LN_LOGV(tc.c);
+                    jac = tc.J;
+                    gj = tc.gj;
                 }
                 if (lane_ok) {
                     XT[xti] = xs;

@@ -411,11 +411,7 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
             }
             xs = q;
             if constexpr (TR) {
-                double J, J2;
-                bf_to_original(q, c_kind, c_lo, c_rg, xs, J, J2);
-                logdet_l = 0. + log(fabs(J));
-                jac = J;
-                gj = J2 / J;
+                bf_to_original<false>(q, c_kind, c_lo, c_rg, xs, jac, logdet_l, gj);
             }
             if (lane_ok) {
                 const int xi = (lane >> 2) * XS + w + 16 * (lane & 3);  // B[k = dim&3][n = chain] of k-step dim>>2

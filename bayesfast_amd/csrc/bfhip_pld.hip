@@ -442,11 +442,9 @@ __global__ __launch_bounds__(NPT * 64) void bf_pld_logp_grad_kernel(DevModel m, 
             jac[e] = 1.;
             gj[e] = 0.;
             if (tr && on[e]) {
-                double J, J2;
-                bf_to_original(xin, (int)m.pd[PD_KIND * DP + dim], m.pd[PD_LO * DP + dim], m.pd[PD_RG * DP + dim], xo[e], J, J2);
-                logdet += log(fabs(J));
-                jac[e] = J;
-                gj[e] = J2 / J;
+                double lj;
+                bf_to_original(xin, (int)m.pd[PD_KIND * DP + dim], m.pd[PD_LO * DP + dim], m.pd[PD_RG * DP + dim], xo[e], jac[e], lj, gj[e]);
+                logdet += lj;
             }
             su_diff[e] = (m.has_su && on[e]) ? m.pd[PD_SU_DIFF * DP + dim] : 1.;
             xs[e] = (m.has_su && on[e]) ? (xo[e] - m.pd[PD_SU_LO * DP + dim]) / su_diff[e] : xo[e];

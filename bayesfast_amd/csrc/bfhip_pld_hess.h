@@ -161,8 +161,8 @@ __device__ inline PldHessPt pldh_eval(const DevModel &m, const double *x, int or
     r.ab = r.cb = r.ib2 = r.q = r.tailc = 0.;
     __syncthreads();   // the previous evaluation's readers are done
     for (int i = tid; i < d; i += nt) {
-        double xo = x[i], J = 1., J2 = 0., lj2 = 0.;
-        if (r.tr) bf_hess_transform(x[i], (int)pd[PD_KIND * DP + i], pd[PD_LO * DP + i], pd[PD_RG * DP + i], xo, J, J2, lj2);
+        double xo = x[i], J = 1., J2 = 0., lj = 0., gj = 0., lj2 = 0.;
+        if (r.tr) bf_hess_transform(x[i], (int)pd[PD_KIND * DP + i], pd[PD_LO * DP + i], pd[PD_RG * DP + i], xo, J, J2, lj, gj, lj2);
         const double diff = m.has_su ? pd[PD_SU_DIFF * DP + i] : 1.;
         const double xs = m.has_su ? (xo - pd[PD_SU_LO * DP + i]) / diff : xo;
         w.xo[i] = xo;
@@ -171,9 +171,9 @@ __device__ inline PldHessPt pldh_eval(const DevModel &m, const double *x, int or
         w.J2[i] = J2;
         w.a[i] = J / diff;
         w.b[i] = J2 / diff;
-        w.lj[i] = r.tr ? log(fabs(J)) : 0.;
+        w.lj[i] = lj;
         w.lj2[i] = lj2;
-        w.gj[i] = r.tr ? J2 / J : 0.;
+        w.gj[i] = gj;
         w.xm[i] = m.use_bound ? xs - pd[PD_MU * DP + i] : 0.;
     }
     __syncthreads();

@@ -1121,27 +1121,17 @@ __global__ __launch_bounds__(BF_SAMPLER_WAVES(W, FULLM, FS) * 64) void bf_sample
                 jac[e] = 1.;
                 gj[e] = 0.;
                 if (PLD && f_tr) {
-                    // (the pipeline instantiation: one INLINED exponential and logarithm for every kind of bound -- the
-                    // out-of-line libm calls of this file cost a round of register spills each at this kernel's pressure;
-                    // the same expressions as bf_to_original_g of the lane-per-chain kernels)
-                    const int kind = (int)pdl(PD_KIND, e);
-                    const double rg = pdl(PD_RG, e);
-                    const double ex = __ocml_exp_f64(kind == 1 ? -q[e] : q[e]);
-                    const double t = 1. / (1. + ex);
-                    double tmp = q[e], jt = 1., gq_ = 0.;
-                    if (kind == 1) { tmp = t; jt = t * (1. - t); gq_ = (ex - 1.) * t; }
-                    if (kind == 2) { tmp = ex; jt = ex; gq_ = 1.; }
-                    if (kind == 3) { tmp = 1. - ex; jt = -ex; gq_ = 1.; }
-                    xo[e] = pdl(PD_LO, e) + tmp * rg;
-                    jac[e] = jt * rg;
-                    gj[e] = gq_;
-                    logdet += __ocml_log_f64(fabs(jac[e]));
+                    // (the pipeline instantiation: the shared transform, bfhip_constraint.h, with an INLINED exponential and
+                    // logarithm -- the out-of-line libm calls of this file cost a round of register spills each at this
+                    // kernel's pressure)
+                    double lj;
+                    bf_to_original<false>(q[e], (int)pdl(PD_KIND, e), pdl(PD_LO, e), pdl(PD_RG, e), xo[e], jac[e], lj, gj[e],
+                                   [](double v) { return __ocml_exp_f64(v); }, [](double v) { return __ocml_log_f64(v); });
+                    logdet += lj;
                 } else if (f_tr) {
-                    double J, J2;
-                    bf_to_original(q[e], (int)pdl(PD_KIND, e), pdl(PD_LO, e), pdl(PD_RG, e), xo[e], J, J2);
-                    logdet += log(fabs(J));
-                    jac[e] = J;
-                    gj[e] = J2 / J;
+                    double lj;
+                    bf_to_original<false>(q[e], (int)pdl(PD_KIND, e), pdl(PD_LO, e), pdl(PD_RG, e), xo[e], jac[e], lj, gj[e]);
+                    logdet += lj;
                 }
                 xs[e] = f_su ? (xo[e] - pdl(PD_SU_LO, e)) / pdl(PD_SU_DIFF, e) : xo[e];
                 double x_eval = xs[e];

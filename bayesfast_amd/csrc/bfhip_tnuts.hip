@@ -149,12 +149,12 @@ __global__ __launch_bounds__(64 * TN_WAVES) void bf_tnuts_kernel(DevModel m, Tnu
         // target surrogate with its bound (modules/poly.py:466-503), behind the constraint transform when there is one
         double x = q, jac = 1., gj = 0., logdet_l = 0.;
         if constexpr (TR) {
-            double J, J2;
-            bf_to_original(q, c_kind, c_lo, c_rg, x, J, J2);
+            double J, lj, g2;
+            bf_to_original<false>(q, c_kind, c_lo, c_rg, x, J, lj, g2);
             if (in) {
-                logdet_l = log(fabs(J));
+                logdet_l = lj;
                 jac = J;
-                gj = J2 / J;
+                gj = g2;
             } else {
                 x = 0.;
             }
@@ -240,7 +240,10 @@ extern "C" int bfhip_tnuts_run(bfhip_ctx *ctx, const bfhip_sampler_config *cfg, 
     a.scratch = (double *)ctx->scratch;
     a.base_S = tp->base_S; a.base_lin = tp->base_lin; a.base_c0 = tp->base_c0; a.logxi = tp->logxi;
     a.cpg = cpg;
-    if (generic) return bf_tnuts_gen_launch(ctx, a, cfg->full_metric ? (const double *)cfg->metric_mat : NULL);
+    if (generic) {
+        snprintf(bf_tune().last_kernel, sizeof(bf_tune().last_kernel), "bf_tnuts_gen_kernel<%d>", m.DP / 16);
+        return bf_tnuts_gen_launch(ctx, a, cfg->full_metric ? (const double *)cfg->metric_mat : NULL);
+    }
     const size_t lds = ((size_t)8 * 16 * TN_XS + TN_WAVES * TN_MAXL * TS_N + 2) * sizeof(double);
     const bool tr = m.has_transform != 0, dec = m.use_decay != 0;
     void (*k)(DevModel, TnutsArgs) = NULL;
@@ -248,6 +251,7 @@ extern "C" int bfhip_tnuts_run(bfhip_ctx *ctx, const bfhip_sampler_config *cfg, 
     k = m.DP == 64 ? TN_PICK(4) : (m.DP == 32 ? TN_PICK(2) : TN_PICK(1));
 #undef TN_PICK
     if (int rc = bf_set_lds(k, lds)) return rc;
+    snprintf(bf_tune().last_kernel, sizeof(bf_tune().last_kernel), "bf_tnuts_kernel<%d, %s, %s>", m.DP / 16, tr ? "true" : "false", dec ? "true" : "false");
     hipLaunchKernelGGL(k, dim3((n_chain + cpg - 1) / cpg), dim3(64 * TN_WAVES), lds, ctx->stream, m, a);
     BF_HIP_CHECK(hipGetLastError());
     return 0;

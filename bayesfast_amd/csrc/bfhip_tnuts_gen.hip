@@ -268,11 +268,9 @@ __global__ __launch_bounds__(64 * TG_WAVES) void bf_tnuts_gen_kernel(DevModel m,
             jac[e] = 1.;
             gj[e] = 0.;
             if (f_tr && in[e]) {
-                double J, J2;
-                bf_to_original(q[e], c_kind[e], c_lo[e], c_rg[e], xo[e], J, J2);
-                logdet_l += log(fabs(J));
-                jac[e] = J;
-                gj[e] = J2 / J;
+                double lj;
+                bf_to_original<false>(q[e], c_kind[e], c_lo[e], c_rg[e], xo[e], jac[e], lj, gj[e]);
+                logdet_l += lj;
             }
             xs[e] = (f_su && in[e]) ? (xo[e] - c_sulo[e]) / c_sudf[e] : xo[e];
             xm[e] = in[e] ? xs[e] - c_mu[e] : 0.;

@@ -150,3 +150,18 @@ extern "C" int bfhost_laplace_opt(const bfhip_density_desc *ds, int max_iter, do
     }
     return 0;
 }
+
+// the constraint transform's one helper (bfhip_constraint.h) at n coordinates of one kind: out[5 i ..] = T, T', log|T'|, T''/T',
+// d2 log|T'| / dx2
+extern "C" int bfhost_constraint(int n, const double *x, int kind, double lo, double rg, double *out) {
+    for (int i = 0; i < n; ++i) {
+        double xo, J, J2, lj, gj, lj2;
+        bf_hess_transform(x[i], kind, lo, rg, xo, J, J2, lj, gj, lj2);
+        out[5 * i + 0] = xo;
+        out[5 * i + 1] = J;
+        out[5 * i + 2] = lj;
+        out[5 * i + 3] = gj;
+        out[5 * i + 4] = lj2;
+    }
+    return 0;
+}

@@ -48,3 +48,13 @@ def maximize(spec, x0, max_iter=200, xtol=1e-5):
     if rc != 0:
         raise RuntimeError('bfhost_laplace_opt failed: %d' % rc)
     return x, logp, hess, info
+
+
+def constraint(x, kind, lo, hi):
+    """x (n,) -> (n, 5): T, T', log|T'|, T''/T', d2 log|T'|/dx2 of ``bfhip_constraint.h`` for one kind and range."""
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    out = np.empty((x.size, 5))
+    rc = lib().bfhost_constraint(C.c_int(x.size), _p(x), C.c_int(int(kind)), C.c_double(float(lo)), C.c_double(float(hi) - float(lo)), _p(out))
+    if rc != 0:
+        raise RuntimeError('bfhost_constraint failed: %d' % rc)
+    return out
