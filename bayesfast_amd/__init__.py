@@ -5,7 +5,7 @@ run as hand-written gfx950 HIP kernels behind a C ABI (include/bfhip.h); this pa
 host side that mirrors the reference's ``modules`` / ``samplers`` / ``core.sample`` interfaces for that path.
 """
 from . import _lib  # noqa: F401
-from .modules import PolyConfig, PolyModel
+from .modules import PolyConfig, PolyModel, FitReport
 from .core.module import Surrogate
 from .core.density import SurrogateDensity, Chi2PipelineDensity, GaussianLink
 from .core.sample import sample
@@ -15,6 +15,6 @@ from .core.refit import select_fit_points, importance_weights
 from .transforms import SIT
 from .evidence import GBS, GIS, GHM, bridge, importance, harmonic
 
-__all__ = ['PolyConfig', 'PolyModel', 'Surrogate', 'SurrogateDensity', 'Chi2PipelineDensity', 'GaussianLink', 'sample', 'NTrace', 'HTrace', 'TNTrace', 'GaussianBase', 'TraceTuple',
+__all__ = ['PolyConfig', 'PolyModel', 'FitReport', 'Surrogate', 'SurrogateDensity', 'Chi2PipelineDensity', 'GaussianLink', 'sample', 'NTrace', 'HTrace', 'TNTrace', 'GaussianBase', 'TraceTuple',
            'SystematicResampler', 'select_fit_points', 'importance_weights', 'SIT', 'GBS', 'GIS', 'GHM', 'bridge', 'importance',
            'harmonic']

@@ -100,6 +100,8 @@ SYMBOLS = {
     'bfhip_tree_size_mode_share': (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_double, _vp]),
     'bfhip_solve_spd': (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     'bfhip_lstsq': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp]),
+    'bfhip_lstsq_loo': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  C.c_size_t]),
     'bfhip_sort_keys': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp]),
     'bfhip_order_keys': (C.c_int, [_vp, C.c_long, _vp, _vp]),
     'bfhip_count_keys': (C.c_int, [_vp, C.c_long, _vp, C.c_long, _vp, C.c_int, _vp]),
@@ -149,6 +151,8 @@ DIAG_BATCH = 16         # BFHIP_DIAG_BATCH: parameters per batch of the bfhip_di
 WSTAT_WORK = 65536      # BFHIP_WSTAT_WORK: doubles of bfhip_wstat_moments' work buffer
 MARG_MAX_BINS, MARG_MAX_BINS2D, MARG_MAX_LD = 1024, 128, 256   # BFHIP_MARG_MAX_BINS / _BINS2D / _LD
 MARG_EXTENT_WORK = 32768   # BFHIP_MARG_EXTENT_WORK: doubles of bfhip_marg_extent's work buffer
+LOO_TILE, LOO_WS_MAX, LOO_NSUM = 64, 1 << 28, 8   # BFHIP_LOO_TILE / _WS_MAX (doubles) / _NSUM
+LOO_SSE, LOO_PRESS, LOO_MAX, LOO_ARGMAX, LOO_SY, LOO_SYY, LOO_NUNIT = range(7)   # BFHIP_LOO_*: the columns of bfhip_lstsq_loo's sums
 WSTAT_TILE = 2048       # sorted positions per workgroup of bfhip_wstat_cumweights: its work buffer is ceil(n / 2048) doubles
 
 

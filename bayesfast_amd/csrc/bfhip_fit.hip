@@ -7,6 +7,7 @@
 // factorisation).
 #include <vector>
 #include "bfhip_common.h"
+#include "bfhip_loo.h"
 
 __device__ inline double bf_readlane(double v, int l) {  // l wave-uniform
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
@@ -845,11 +846,16 @@ __global__ void bf_axpy_kernel(int n, double *__restrict__ x, const double *__re
     if (i < n) x[i] += dx[i];
 }
 
-extern "C" int bfhip_lstsq(bfhip_ctx *ctx, int n, int P, int m, const double *A, int lda, const double *B, double *G, double *c,
-                           int n_refine, double *work, int *info) {
+// The one implementation of bfhip_lstsq and bfhip_lstsq_loo: without h, e_loo and sums it is the plain solve, launch for launch.
+static int lstsq_impl(bfhip_ctx *ctx, const char *who, int n, int P, int m, const double *A, int lda, const double *B, double *G,
+                      double *c, int n_refine, double *work, int *info, double *h, double *e_loo, double *sums, const double *w,
+                      double *ws, size_t ws_doubles) {
     BfDeviceGuard dev_guard(ctx);
+    const bool loo = h || e_loo || sums;
     if (!ctx || n < 1 || P < 1 || m < 1 || !A || !B || !G || !c || !info || lda < P || n_refine < 0 || (n_refine > 0 && !work))
-        return bf_set_error(BFHIP_ERR_ARG, "bfhip_lstsq: invalid argument");
+        return bf_set_error(BFHIP_ERR_ARG, "%s: invalid argument", who);
+    if (loo && (!h || !e_loo || !sums || !work || !ws || ws_doubles < (size_t)((P + NB_ - 1) / NB_) * NB_ * BFHIP_LOO_TILE))
+        return bf_set_error(BFHIP_ERR_ARG, "%s: h, e_loo and sums come together, with work and a workspace of at least one tile", who);
     if (int rc = bfhip_gram(ctx, n, P, m, A, lda, B, G, c)) return rc;
     // (the Gram scratch is free again; the scales and the block inverse live behind the A^T S partials of the refinement)
     const size_t n_atb = (size_t)ATB_SEG_ * m * P, n_inv = (size_t)((P + NB_ - 1) / NB_) * NB_ * NB_;
@@ -866,6 +872,24 @@ extern "C" int bfhip_lstsq(bfhip_ctx *ctx, int n, int P, int m, const double *A,
         if (int rc = chol_apply(ctx, P, m, G, dsc, LinvAll, dc, true)) return rc;
         hipLaunchKernelGGL(bf_axpy_kernel, dim3((P * m + 255) / 256), dim3(256), 0, st, P * m, c, dc);
     }
+    if (loo) {
+        // the residual at the coefficients that are returned; the scales and the block inverses are still where the factorisation
+        // left them (nothing since has grown ctx->scratch: chol_apply only ever grows ctx->flow, and the leverages run in the
+        // caller's workspace)
+        hipLaunchKernelGGL(bf_resid_kernel, dim3((n + 3) / 4), dim3(256), 0, st, n, P, m, A, lda, B, c, S);
+        if (int rc = bf_leverage_launch(ctx, n, P, A, lda, G, dsc, LinvAll, info, h, ws, ws_doubles)) return rc;
+        if (int rc = bf_loo_sums_launch(ctx, n, m, S, B, h, w, info, e_loo, sums)) return rc;
+    }
     BF_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+extern "C" int bfhip_lstsq(bfhip_ctx *ctx, int n, int P, int m, const double *A, int lda, const double *B, double *G, double *c,
+                           int n_refine, double *work, int *info) {
+    return lstsq_impl(ctx, "bfhip_lstsq", n, P, m, A, lda, B, G, c, n_refine, work, info, NULL, NULL, NULL, NULL, NULL, 0);
+}
+extern "C" int bfhip_lstsq_loo(bfhip_ctx *ctx, int n, int P, int m, const double *A, int lda, const double *B, double *G, double *c,
+                               int n_refine, double *work, int *info, double *h, double *e_loo, double *sums, const double *w,
+                               double *ws, size_t ws_doubles) {
+    return lstsq_impl(ctx, "bfhip_lstsq_loo", n, P, m, A, lda, B, G, c, n_refine, work, info, h, e_loo, sums, w, ws, ws_doubles);
 }

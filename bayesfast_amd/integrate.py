@@ -73,11 +73,28 @@ def reference_classes(bayesfast=None):
             return _OurModel(cfgs, input_size=int(self._input_size), output_size=int(self._output_size),
                              bound_options=dict(use_bound=False))
 
+        # as on ``bayesfast_amd.PolyModel``: with ``loo_on_fit`` set, ``fit`` -- which is all an unmodified Recipe calls -- leaves
+        # the leave-one-out validation of the fit (a ``FitReport``) in ``fit_report``
+        loo_on_fit = False
+        fit_report = None
+
+        def fit_loo(self, x, y, logp=None, w=None):
+            """``fit`` with the leave-one-out ``FitReport`` of ``bayesfast_amd.PolyModel.fit_loo``."""
+            on = self.loo_on_fit
+            self.loo_on_fit = True
+            try:
+                self.fit(x, y, logp, w)
+            finally:
+                self.loo_on_fit = on
+            return self.fit_report
+
         def fit(self, x, y, logp=None, w=None):
             """modules/poly.py:505-589 with the per-output ``lstsq`` (:570) replaced by the device solve; the argument
             checks are those of ``bayesfast_amd.PolyModel.fit`` (same conditions and messages as :509-526)."""
             mirror = self._device_mirror()
+            mirror.loo_on_fit = bool(self.loo_on_fit)
             _device_fit(mirror, x, y, logp, w)
+            self.fit_report = mirror.fit_report
             for mine, fitted in zip(self.configs, mirror.configs):
                 coef = np.ascontiguousarray(fitted._coef, dtype=np.float64)
                 if coef.shape != tuple(mine._A_shape):

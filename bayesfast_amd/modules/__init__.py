@@ -1,3 +1,4 @@
 from .poly import PolyConfig, PolyModel
+from .fit_report import FitReport
 
-__all__ = ['PolyConfig', 'PolyModel']
+__all__ = ['PolyConfig', 'PolyModel', 'FitReport']

@@ -22,6 +22,10 @@ from ..core.module import Surrogate
 
 __all__ = ['PolyConfig', 'PolyModel']
 
+# doubles of workspace one ``fit_loo`` group may take for the leverage kernel's tiles in flight (BFHIP_LOO_WS_MAX: more is not
+# used); at least one tile's slice is always given.  A smaller value only means more passes: the numbers do not change.
+LOO_WORKSPACE_DOUBLES = _lib.LOO_WS_MAX
+
 BoundOptions = namedtuple('BoundOptions', ('use_bound', 'alpha', 'alpha_p', 'center_max'))
 _ORDERS = ('linear', 'quadratic', 'cubic-2', 'cubic-3')
 
@@ -287,10 +291,26 @@ class PolyModel(Surrogate):
     # ---- fit ----
     _N_REFINE = 2  # refinement steps of the least-squares solve
 
+    # ``fit()`` runs the ``fit_loo`` route and leaves its report in ``fit_report`` (None before, and after any plain fit): how a
+    # caller that only knows ``fit`` -- the reference's Recipe -- gets the validation
+    loo_on_fit = False
+    fit_report = None
+
     def fit(self, x, y, logp=None, w=None):
         """Fit the polynomial model (modules/poly.py:505-589) on device.
 
         x (n, input_size), y (n, output_size); logp (n,) is only used for ``center_max``; w (n,) row weights."""
+        self.fit_report = self._fit(x, y, logp, w, bool(self.loo_on_fit))
+
+    def fit_loo(self, x, y, logp=None, w=None):
+        """``fit``, and the leave-one-out validation of the fit it has made: a ``FitReport`` (modules/fit_report.py) with the
+        leverage of every fit point, the residuals, the residuals each point would have under a fit without it (exact for least
+        squares: e_i / (1 - h_i), no refit and no call of the true model) and per output rmse, loo_rmse, r2 and q2.  The
+        leverages cost n P^2 operations on the device, a few times the fit itself."""
+        self.fit_report = self._fit(x, y, logp, w, True)
+        return self.fit_report
+
+    def _fit(self, x, y, logp, w, loo):
         import torch
         from ..device import get_context, _ptr
         x = np.asarray(x)
@@ -319,7 +339,9 @@ class PolyModel(Surrogate):
         for ii in range(self._output_size):
             groups.setdefault(tuple(int(v) for v in self._recipe[ii]), []).append(ii)
         pending = []
-        for key, outs in groups.items():
+        group_of_output = np.zeros(self._output_size, dtype=int)
+        for gi, (key, outs) in enumerate(groups.items()):
+            group_of_output[outs] = gi
             confs = [self._configs[k] for k in key if k >= 0]
             widths = [c._a_shape[0] for c in confs]
             P = int(sum(widths))
@@ -338,13 +360,28 @@ class PolyModel(Surrogate):
             # normal equations + two refinement steps on the true residual: the accuracy of an orthogonal factorisation
             # for every design the pivot threshold lets through (include/bfhip.h: bfhip_lstsq)
             work = ctx.empty((n * len(outs) + P * len(outs),))
-            _lib.check(lib.bfhip_lstsq(h, n, P, len(outs), _ptr(A), P, _ptr(B), _ptr(G), _ptr(r), self._N_REFINE, _ptr(work),
-                                       _ptr(info)))
-            pending.append((outs, confs, widths, P, A, B, G, r, info, work))
+            val = None
+            if loo:
+                # the tiles of design rows that the leverage kernel takes through the factor side by side (include/bfhip.h)
+                slice_ = -(-P // 64) * 64 * _lib.LOO_TILE
+                n_ws = max(slice_, min(-(-n // _lib.LOO_TILE) * slice_, int(LOO_WORKSPACE_DOUBLES) // slice_ * slice_))
+                val = dict(outs=outs, h=ctx.empty((n,)), e_loo=ctx.empty((n, len(outs))), sums=ctx.empty((len(outs), _lib.LOO_NSUM)))
+                ws = val['ws'] = ctx.empty((n_ws,))   # (kept, like every buffer of the solve, until the device is waited for below)
+                _lib.check(lib.bfhip_lstsq_loo(h, n, P, len(outs), _ptr(A), P, _ptr(B), _ptr(G), _ptr(r), self._N_REFINE, _ptr(work),
+                                               _ptr(info), _ptr(val['h']), _ptr(val['e_loo']), _ptr(val['sums']), _ptr(wt), _ptr(ws),
+                                               n_ws))
+            else:
+                _lib.check(lib.bfhip_lstsq(h, n, P, len(outs), _ptr(A), P, _ptr(B), _ptr(G), _ptr(r), self._N_REFINE, _ptr(work),
+                                           _ptr(info)))
+            pending.append((outs, confs, widths, P, A, B, G, r, info, work, val))
         # the bound's statistics are host work on x alone: they run while the device solves
         bound = self._bound_stats(x, logp) if (self._use_bound and not self._all_linear) else None
-        for outs, confs, widths, P, A, B, G, r, info, work in pending:
-            if int(info.item()) != 0:
+        rank_deficient = []
+        for outs, confs, widths, P, A, B, G, r, info, work, val in pending:
+            rank_deficient.append(int(info.item()) != 0)
+            if val is not None:
+                del val['ws']
+            if rank_deficient[-1]:
                 # numerically rank-deficient design matrix: LAPACK gelsd (modules/poly.py:570) returns the MINIMUM-NORM solution
                 # x = A^+ b, and so does this path (round 6; a ridge-regularised solve before, another member of the solution set):
                 # with G = A^T A = V diag(lam) V^T, x = V_k diag(1 / lam_k) V_k^T A^T b over the eigenvalues above the cut, then
@@ -367,7 +404,25 @@ class PolyModel(Surrogate):
                     res = B - A @ sol_t
                     sol_t = sol_t + Vk @ (ilam[:, None] * (Vk.T @ (A.T @ res)))
                 r.copy_(sol_t)
+                if val is not None:
+                    # the leverages of the same kept subspace, h_i = | diag(lam_k^-1/2) V_k^T a_i |^2 (they sum to its rank), and
+                    # the sums the kernels would have made (modules/fit_report.py: SUM_NAMES)
+                    T = A @ Vk
+                    val['h'] = (T * T * ilam[None, :]).sum(1)
+                    S = B - A @ sol_t
+                    d = 1. - val['h']
+                    s_loo = torch.where(d[:, None] > 0., S / d[:, None], torch.where(S < 0., -np.inf, np.inf).to(S.dtype))
+                    val['e_loo'] = s_loo if wt is None else s_loo / wt[:, None]
+                    val['resid'] = S if wt is None else S / wt[:, None]
+                    al = val['e_loo'].abs()
+                    zero = torch.zeros_like(S[0])
+                    val['sums'] = torch.stack([(S * S).sum(0), (s_loo * s_loo).sum(0), al.max(0).values, al.argmax(0).to(S.dtype),
+                                               B.sum(0), (B * B).sum(0), zero + float((d <= 0.).sum()), zero], dim=1)
                 ctx.stream.wait_stream(torch.cuda.current_stream(ctx.device))
+            elif val is not None:
+                torch.cuda.current_stream(ctx.device).wait_stream(ctx.stream)
+                S = work[:n * len(outs)].view(n, len(outs))   # B - A c at the returned coefficients
+                val['resid'] = S.clone() if wt is None else S / wt[:, None]
             sol = r.cpu().numpy()
             for jo, ii in enumerate(outs):
                 k = 0
@@ -375,10 +430,15 @@ class PolyModel(Surrogate):
                     qq = int(np.argwhere(c._output_mask == ii)[0, 0])
                     c._set(sol[k:k + wd, jo], qq)
                     k += wd
+        report = None
+        if loo:
+            from .fit_report import FitReport
+            report = FitReport(n, [p[3] for p in pending], group_of_output, [p[10] for p in pending], rank_deficient)
         del pending
         self._touch()   # a refit: every device copy built before it is stale
         if bound is not None:
             self._apply_bound(*bound)
+        return report
 
     def _bound_stats(self, x, logp=None):
         """The part of ``_set_bound`` that only needs the fit points: mu, H = inv(cov), alpha and the point f_mu is taken at

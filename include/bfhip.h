@@ -37,7 +37,9 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_DIM 128         /* input_size limit of the device path */
 #define BFHIP_MAX_TREEDEPTH 12
 
-/* 108: bfhip_marg_quantise / _extent / _hist1d / _index / _hist2d / _levels, the marginal posterior histograms and their credible levels
+/* 109: bfhip_lstsq_loo, the leave-one-out validation of the least-squares fit (leverages from the kept factor, held-out residuals,
+ * per-output sums).
+ * 108: bfhip_marg_quantise / _extent / _hist1d / _index / _hist2d / _levels, the marginal posterior histograms and their credible levels
  * (additions only: the number stays).  bfhip_wave_packs_probe; bfhip_psis and bfhip_wstat_columns / _moments / _cumweights / _quantiles, the Pareto-smoothed importance
  * weights and the weighted posterior table (additions only: the number stays).
  * 107: bfhip_pipeline_logp_hess and bfhip_pipeline_laplace_opt, the analytic and the Gauss-Newton Hessian of the pipeline density and
@@ -378,6 +380,37 @@ int bfhip_solve_spd(bfhip_ctx *ctx, int P, int m, double *G, double *r, int *inf
  * (two steps: 1e-10 of the coefficient scale, tests/golden/fit_illcond.npz). */
 int bfhip_lstsq(bfhip_ctx *ctx, int n, int P, int m, const double *A, int lda, const double *B, double *G, double *c,
                 int n_refine, double *work, int *info);
+
+/* bfhip_lstsq with the leave-one-out validation of the fit it has just made (PolyModel.fit_loo).  For linear least squares the
+ * residual of row i under a fit without row i is S_i / (1 - h_i) exactly, h_i = a_i^T (A^T A)^-1 a_i = | L^-1 D a_i |^2 the
+ * leverage of design row a_i: no refit, n P^2 operations with the kept factor, on the FP64 matrix cores.  The first twelve
+ * arguments, c, G and info are bfhip_lstsq's (the same launches, the same bits); after the refinement
+ *   h (n,)        the leverages;
+ *   e_loo (n, m)  S / ((1 - h) w), S = B - A c at the returned c: the held-out residuals in the units of B / w (w (n,) are the
+ *                 row weights A and B were built with, NULL for none).  A row with 1 - h <= 0 after rounding gets +-inf;
+ *   sums (m, BFHIP_LOO_NSUM)  per output, summed over the rows in a fixed order, in the units of B (the weighted ones):
+ *                 [BFHIP_LOO_SSE] sum S^2, [_PRESS] sum (S / (1 - h))^2, [_MAX] max |e_loo| and [_ARGMAX] its (first) row,
+ *                 [_SY] sum B, [_SYY] sum B^2, [_NUNIT] the number of rows with 1 - h <= 0 (their infinities are in _PRESS and
+ *                 _MAX too), [7] zero.
+ * h, e_loo and sums are given together or all NULL; all NULL is bfhip_lstsq exactly (w, ws unused, nothing more is launched).
+ * Otherwise work (n m + P m doubles) is needed whatever n_refine, and ws, a workspace of ws_doubles doubles: a workgroup takes
+ * BFHIP_LOO_TILE design rows through the factor and keeps its part of L^-1 D a in a slice of ceil(P / 64) * 64 * BFHIP_LOO_TILE
+ * doubles, so the workspace holds ws_doubles / slice tiles side by side and the rows are taken in as many passes as that asks
+ * for (BFHIP_ERR_ARG if it holds none).  No more than BFHIP_LOO_WS_MAX doubles (2 GiB) of it are used.  Two calls give the same
+ * bits, whatever the workspace's size.  info != 0 (rank deficiency): h, e_loo and sums are left untouched. */
+#define BFHIP_LOO_TILE 64
+#define BFHIP_LOO_WS_MAX (1L << 28)
+#define BFHIP_LOO_NSUM 8
+#define BFHIP_LOO_SSE 0
+#define BFHIP_LOO_PRESS 1
+#define BFHIP_LOO_MAX 2
+#define BFHIP_LOO_ARGMAX 3
+#define BFHIP_LOO_SY 4
+#define BFHIP_LOO_SYY 5
+#define BFHIP_LOO_NUNIT 6
+int bfhip_lstsq_loo(bfhip_ctx *ctx, int n, int P, int m, const double *A, int lda, const double *B, double *G, double *c,
+                    int n_refine, double *work, int *info, double *h, double *e_loo, double *sums, const double *w, double *ws,
+                    size_t ws_doubles);
 
 /* ------------------------------------------------------------------------------------------------
  * Refit glue: the steps either side of the sampler inside Recipe._sam_step / _pos_step.
