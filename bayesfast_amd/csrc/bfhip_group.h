@@ -42,9 +42,13 @@
 // (profiles/r06b_trace_pld_des.log); here the 16 chains of a group share every instruction of it.  The evaluation is always "late"
 // (the gradient needs the contractions' result): phase A | B1 | the bound's tiles, sums | B2 | evaluation points | P0 | monomials |
 // P1 | F = C' Phi | P2 | W = C'^T r | P3 | gradient gather, second half step, U-turn sums | B3 | the state machine as before.
+//
+// Rounding: this header and bfhip_split.h are built with -ffp-contract=off (bfhip_group.hip, tests/emu), an fma is written where one
+// is meant; the iteration end -- step size, statistics, the metric's windows -- is bfhip_adapt.h with FUSED = false.
 #pragma once
 #include "bfhip_lane.h"
 #include "bfhip_constraint.h"
+#include "bfhip_adapt.h"
 #include "bfhip_sampler_defs.h"
 #include "bfhip_oob.h"
 #include "bfhip_pld.h"
@@ -115,6 +119,19 @@ struct BfLaneExp {
     double operator()(double x) const { return bf_exp(x); }
 #else
     __device__ __forceinline__ double operator()(double x) const { return bf_exp(x); }
+#endif
+};
+
+// math policy of the iteration end (bfhip_adapt.h) in the group and split kernels
+struct BfLaneMath {
+#ifdef BF_HOST_EMU
+    static double ex(double x) { return bf_exp(x); }
+    static double lg(double x) { return bf_log(x); }
+    static double sq(double x) { return bf_sqrt(x); }
+#else
+    static __device__ __forceinline__ double ex(double x) { return bf_exp(x); }
+    static __device__ __forceinline__ double lg(double x) { return bf_log(x); }
+    static __device__ __forceinline__ double sq(double x) { return bf_sqrt(x); }
 #endif
 };
 
@@ -212,7 +229,7 @@ BF_DEV void bf_group_body(const DevModel &m, const SamplerArgs &a, double *lds) 
     double h_acc = 0., h_de = 0., h_end_E = 0., h_end_logp = 0.;
     double log_step = 0., log_bar = 0., hbar = 0., smu = 0., count = 1., step_now = 0., step_bar = 0.;
     // Welford window counters (metrics.py:186-211): every lane of a chain keeps its own copy in step
-    double fg_n = 0., bg_n = 0., n_samples = 0., prev_upd = 0., adapt_window = 0.;
+    BfMetricWindow mw = {0., 0., 0., 0., 0.};
     bool need_E0 = false;     // the running iteration's start energy waits for its kinetic part (this trip's exchange)
     double kin0_part = 0.;
     unsigned long long nlf = 0;
@@ -397,11 +414,11 @@ BF_DEV void bf_group_body(const DevModel &m, const SamplerArgs &a, double *lds) 
         hbar = scp[BFHIP_SC_HBAR];
         smu = scp[BFHIP_SC_MU];
         count = scp[BFHIP_SC_COUNT];
-        fg_n = scp[BFHIP_SC_FG_N];
-        bg_n = scp[BFHIP_SC_BG_N];
-        n_samples = scp[BFHIP_SC_N_SAMPLES];
-        prev_upd = scp[BFHIP_SC_PREV_UPDATE];
-        adapt_window = scp[BFHIP_SC_ADAPT_WINDOW];
+        mw.fg_n = scp[BFHIP_SC_FG_N];
+        mw.bg_n = scp[BFHIP_SC_BG_N];
+        mw.n_samples = scp[BFHIP_SC_N_SAMPLES];
+        mw.prev_upd = scp[BFHIP_SC_PREV_UPDATE];
+        mw.adapt_window = scp[BFHIP_SC_ADAPT_WINDOW];
         step_now = bf_exp(log_step);   // exp(log_step), exp(log_bar): what the statistics report
         step_bar = bf_exp(log_bar);
         i_iter = (int)scp[BFHIP_SC_I_ITER];
@@ -1260,12 +1277,7 @@ BF_DEV void bf_group_body(const DevModel &m, const SamplerArgs &a, double *lds) 
             const bool warm = i_iter < nw;
             const double accept_stat = NUTS ? acc_sum / (double)n_prop : h_acc;  // nuts.py:186
             if (warm && a.cfg.adapt_step_size) {  // step_size.py:31-45
-                const double wgt = 1. / (count + a.cfg.t_0);
-                hbar = ((1. - wgt) * hbar + wgt * (a.cfg.target_accept - accept_stat));
-                log_step = smu - hbar * bf_sqrt(count) / a.cfg.gamma;
-                const double mk = bf_exp(-a.cfg.k * bf_log(count));  // count ** -k
-                log_bar = mk * log_step + (1. - mk) * log_bar;
-                count = count + 1.;
+                BfStepAdapt<false>::step(a.cfg, accept_stat, smu, hbar, log_step, log_bar, count, BfLaneMath());
                 step_now = bf_exp(log_step);
                 step_bar = bf_exp(log_bar);
             }
@@ -1280,71 +1292,43 @@ BF_DEV void bf_group_body(const DevModel &m, const SamplerArgs &a, double *lds) 
 #endif
                 if (writer) {
                     double *sp = a.stats + ((size_t)chain * a.n_out + orow) * BFHIP_STAT_STRIDE;
-                    if (NUTS) {
-                        sp[BFHIP_NS_LOGP] = prop_logp;
-                        sp[BFHIP_NS_ENERGY] = prop_E;
-                        sp[BFHIP_NS_TREE_DEPTH] = (double)depth;
-                        sp[BFHIP_NS_TREE_SIZE] = (double)n_prop;
-                        sp[BFHIP_NS_MEAN_TREE_ACCEPT] = accept_stat;
-                        sp[BFHIP_NS_STEP_SIZE] = step_now;
-                        sp[BFHIP_NS_STEP_SIZE_BAR] = step_bar;
-                        sp[BFHIP_NS_WARMUP] = warm ? 1. : 0.;
-                        sp[BFHIP_NS_ENERGY_CHANGE] = prop_E - start_energy;
-                        sp[BFHIP_NS_MAX_ENERGY_CHANGE] = max_de;
-                        sp[BFHIP_NS_DIVERGING] = (double)diverged;
-                    } else {
-                        sp[BFHIP_HS_LOGP] = h_end_logp;
-                        sp[BFHIP_HS_ENERGY] = h_end_E;
-                        sp[BFHIP_HS_N_INT_STEP] = (double)a.cfg.n_int_step;
-                        sp[BFHIP_HS_ACCEPT_STAT] = accept_stat;
-                        sp[BFHIP_HS_ACCEPTED] = (double)h_accepted;
-                        sp[BFHIP_HS_STEP_SIZE] = step_now;
-                        sp[BFHIP_HS_STEP_SIZE_BAR] = step_bar;
-                        sp[BFHIP_HS_WARMUP] = warm ? 1. : 0.;
-                        sp[BFHIP_HS_ENERGY_CHANGE] = h_de;
-                        sp[BFHIP_HS_DIVERGING] = (double)diverged;
-                        sp[10] = 0.;
-                    }
+                    if (NUTS)
+                        bf_stats_row_nuts(sp, prop_logp, prop_E, depth, n_prop, accept_stat, step_now, step_bar, warm, start_energy, max_de,
+                                          diverged);
+                    else
+                        bf_stats_row_hmc(sp, h_end_logp, h_end_E, a.cfg.n_int_step, accept_stat, h_accepted, step_now, step_bar, warm, h_de,
+                                         diverged);
                 }
                 double *xp = a.samples + ((size_t)chain * a.n_out + orow) * d;
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (dbase + 4 * r < d) xp[dbase + 4 * r] = q[r];
             }
-            // QuadMetricDiagAdapt.update: metrics.py:186-211, _WeightedVariance.add_sample :354-360
+            // QuadMetricDiagAdapt.update: metrics.py:186-211
             if (warm && a.cfg.adapt_metric) {
-                const long delta = (long)(n_samples - prev_upd);
+                const long delta = mw.begin();
                 double fm[4], fr[4], bm[4], br[4];
                 load_vec(BFHIP_VEC_FG_MEAN, fm, 0.);
                 load_vec(BFHIP_VEC_FG_RAW, fr, 0.);
                 load_vec(BFHIP_VEC_BG_MEAN, bm, 0.);
                 load_vec(BFHIP_VEC_BG_RAW, br, 0.);
-                fg_n += 1.;
-                bg_n += 1.;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    double od = q[r] - fm[r];
-                    fm[r] += od / fg_n;
-                    fr[r] += 1. * od * (q[r] - fm[r]);
-                    od = q[r] - bm[r];
-                    bm[r] += od / bg_n;
-                    br[r] += 1. * od * (q[r] - bm[r]);
+                    bf_welford_add<false>(q[r], mw.fg_n, fm[r], fr[r]);
+                    bf_welford_add<false>(q[r], mw.bg_n, bm[r], br[r]);
                 }
-                if ((delta + 1) % (long)a.cfg.update_window == 0) {  // metrics.py:181-184
+                if (mw.refresh(a.cfg, delta)) {  // metrics.py:181-184
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        if (dbase + 4 * r < d) { var[r] = fr[r] / fg_n; isd[r] = 1. / bf_sqrt(var[r]); }
+                        if (dbase + 4 * r < d) { var[r] = fr[r] / mw.fg_n; isd[r] = 1. / bf_sqrt(var[r]); }
                     store_vec(BFHIP_VEC_VAR, var);
                 }
-                if ((double)delta >= adapt_window) {
+                const bool roll = mw.roll(delta);
+                if (roll) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { fm[r] = bm[r]; fr[r] = br[r]; bm[r] = 0.; br[r] = 0.; }
-                    fg_n = bg_n;
-                    bg_n = 10.;
-                    prev_upd = n_samples;
-                    if (a.cfg.doubling) adapt_window *= 2.;
                 }
-                n_samples += 1.;
+                mw.end(a.cfg, roll);
                 store_vec(BFHIP_VEC_FG_MEAN, fm);
                 store_vec(BFHIP_VEC_FG_RAW, fr);
                 store_vec(BFHIP_VEC_BG_MEAN, bm);
@@ -1389,11 +1373,11 @@ BF_DEV void bf_group_body(const DevModel &m, const SamplerArgs &a, double *lds) 
             scp[BFHIP_SC_LOG_BAR] = log_bar;
             scp[BFHIP_SC_HBAR] = hbar;
             scp[BFHIP_SC_COUNT] = count;
-            scp[BFHIP_SC_FG_N] = fg_n;
-            scp[BFHIP_SC_BG_N] = bg_n;
-            scp[BFHIP_SC_N_SAMPLES] = n_samples;
-            scp[BFHIP_SC_PREV_UPDATE] = prev_upd;
-            scp[BFHIP_SC_ADAPT_WINDOW] = adapt_window;
+            scp[BFHIP_SC_FG_N] = mw.fg_n;
+            scp[BFHIP_SC_BG_N] = mw.bg_n;
+            scp[BFHIP_SC_N_SAMPLES] = mw.n_samples;
+            scp[BFHIP_SC_PREV_UPDATE] = mw.prev_upd;
+            scp[BFHIP_SC_ADAPT_WINDOW] = mw.adapt_window;
             scp[BFHIP_SC_I_ITER] = (double)i_iter;
             scp[BFHIP_SC_ERROR] = (double)err;
             if (a.n_leapfrog && nlf) bf_atomic_add_u64(a.n_leapfrog, nlf);

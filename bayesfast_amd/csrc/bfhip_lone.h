@@ -43,8 +43,8 @@
 #undef sqrt
 #undef sincospi
 // (the out-of-line wrappers round their argument and their result as the call boundary does; inlined, the library's first and
-// last operations could contract with the caller's -- step sizes one ulp off the pipelined kernel's were the symptom -- so
-// arguments and results pass through an opaque register move)
+// last operations could contract with the caller's, so arguments and results pass through an opaque register move.  Which
+// operations of the iteration end ARE fused is decided in bfhip_adapt.h -- FUSED = true, as in the pipelined kernel -- not here.)
 __device__ inline double ln_opq(double x) { asm("" : "+v"(x)); return x; }
 #define LN_EXPV(x) ln_opq(exp(ln_opq(x)))
 #define LN_LOGV(x) ln_opq(log(ln_opq(x)))
@@ -52,6 +52,12 @@ __device__ inline double ln_opq(double x) { asm("" : "+v"(x)); return x; }
 #define LN_EXP(x) rfl(LN_EXPV(x))
 #define LN_LOG(x) rfl(LN_LOGV(x))
 #define LN_SQRT(x) rfl(LN_SQRTV(x))
+// math policy of the iteration end (bfhip_adapt.h): the inline libm behind the opaque moves, wave-uniform
+struct LnMath {
+    static __device__ __forceinline__ double ex(double x) { return LN_EXP(x); }
+    static __device__ __forceinline__ double lg(double x) { return LN_LOG(x); }
+    static __device__ __forceinline__ double sq(double x) { return LN_SQRT(x); }
+};
 
 enum { LN_CONT = 0, LN_NEW = 1, LN_DONE = 2 };
 enum { LF_NONE = 0, LF_LEAF = 1, LF_INIT = 2 };
@@ -408,7 +414,7 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
     int kb = 0;
     // step_size.py:31-45: what the update at the iteration's end needs of `count` alone -- sqrt(count), count ** -k, 1 / (count + t_0)
     // -- is taken in the window after a tree starts, when this wave has nothing to account for (the same expressions, earlier)
-    double ad_sq = 0., ad_mk = 0., ad_wgt = 0.;
+    BfStepConsts ad = {0., 0., 0.};
     bool ad_ready = false;
     double inv_sd = 0.;   // 1 / sqrt(var): metrics.py:83-86 divides every draw by it; it changes when the metric does
     double *WF = lds + LG::o_WF;   // the Welford windows of the metric (metrics.py:333-371) staged in LDS, written through to the state
@@ -430,9 +436,7 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
     };
     auto adapt_consts = [&]() {
         if (!ad_ready && i_iter < nw && a.cfg.adapt_step_size) {
-            ad_wgt = 1. / (count + a.cfg.t_0);
-            ad_sq = LN_SQRT(count);
-            ad_mk = LN_EXP(-a.cfg.k * LN_LOG(count));  // count ** -k
+            ad = BfStepAdapt<true>::consts(a.cfg, count, LnMath());
             ad_ready = true;
         }
     };
@@ -711,14 +715,7 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
                     const double accept_stat = acc_sum / (double)n_prop;  // nuts.py:186
                     if (warm && a.cfg.adapt_step_size) {  // step_size.py:31-45
                         adapt_consts();   // (normally taken long ago)
-                        const double wgt = ad_wgt;
-                        // (the contractions below are bf_nuts_pipe_kernel's, spelled out: left to the compiler this kernel fused the other
-                        // product of each sum and its step sizes came out an ulp off)
-                        hbar = __builtin_fma(wgt, (a.cfg.target_accept - accept_stat), (1. - wgt) * hbar);
-                        log_step = smu - hbar * ad_sq / a.cfg.gamma;
-                        const double mk = ad_mk;
-                        log_bar = __builtin_fma(mk, log_step, (1. - mk) * log_bar);
-                        count = count + 1.;
+                        BfStepAdapt<true>::update(a.cfg, ad, accept_stat, smu, hbar, log_step, log_bar, count);
                         ad_ready = false;
                         const double e1 = LN_EXPV(log_step), e2 = LN_EXPV(log_bar);   // (one block: side by side)
                         step_now = rfl(e1);
@@ -726,64 +723,42 @@ __global__ __launch_bounds__((LoneWaves<W, DEC, FORM>::NW * 64), MINW) void bf_l
                     }
                     const int orow = i_iter - a.iter_out0;
                     if (orow >= 0 && orow < a.n_out) {
-                        if (lane == 0) {
-                            double *st = a.stats + ((size_t)chain * a.n_out + orow) * BFHIP_STAT_STRIDE;
-                            st[BFHIP_NS_LOGP] = prop_logp;
-                            st[BFHIP_NS_ENERGY] = prop_E;
-                            st[BFHIP_NS_TREE_DEPTH] = (double)depth;
-                            st[BFHIP_NS_TREE_SIZE] = (double)n_prop;
-                            st[BFHIP_NS_MEAN_TREE_ACCEPT] = accept_stat;
-                            st[BFHIP_NS_STEP_SIZE] = step_now;
-                            st[BFHIP_NS_STEP_SIZE_BAR] = step_bar;
-                            st[BFHIP_NS_WARMUP] = warm ? 1. : 0.;
-                            st[BFHIP_NS_ENERGY_CHANGE] = prop_E - start_energy;
-                            st[BFHIP_NS_MAX_ENERGY_CHANGE] = max_de;
-                            st[BFHIP_NS_DIVERGING] = (double)diverged;
-                        }
+                        if (lane == 0)
+                            bf_stats_row_nuts(a.stats + ((size_t)chain * a.n_out + orow) * BFHIP_STAT_STRIDE, prop_logp, prop_E, depth, n_prop,
+                                              accept_stat, step_now, step_bar, warm, start_energy, max_de, diverged);
                         double *sp = a.samples + ((size_t)chain * a.n_out + orow) * d;
                         if (lane < d) sp[lane] = q;
                     }
-                    // QuadMetricDiagAdapt.update: metrics.py:186-211, _WeightedVariance.add_sample :354-360
+                    // QuadMetricDiagAdapt.update: metrics.py:186-211
                     if (warm && a.cfg.adapt_metric) {
-                        double fg_n = rfl(WF[4 * DP + 0]), bg_n = rfl(WF[4 * DP + 1]);
-                        double n_samples = rfl(WF[4 * DP + 2]), prev_upd = rfl(WF[4 * DP + 3]);
-                        double adapt_window = rfl(WF[4 * DP + 4]);
-                        const long delta = (long)(n_samples - prev_upd);
+                        BfMetricWindow mw{rfl(WF[4 * DP + 0]), rfl(WF[4 * DP + 1]), rfl(WF[4 * DP + 2]), rfl(WF[4 * DP + 3]),
+                                          rfl(WF[4 * DP + 4])};
+                        const long delta = mw.begin();
                         double fm = lane_ok ? WF[lane] : 0., fr = lane_ok ? WF[DP + lane] : 0.;
                         double bm = lane_ok ? WF[2 * DP + lane] : 0., br = lane_ok ? WF[3 * DP + lane] : 0.;
-                        fg_n += 1.;
-                        bg_n += 1.;
-                        double od = q - fm;
-                        fm += od / fg_n;
-                        fr += 1. * od * (q - fm);
-                        od = q - bm;
-                        bm += od / bg_n;
-                        br += 1. * od * (q - bm);
-                        if ((delta + 1) % (long)a.cfg.update_window == 0) {  // metrics.py:181-184
-                            if (lane < d) var = fr / fg_n;
+                        bf_welford_add<true>(q, mw.fg_n, fm, fr);
+                        bf_welford_add<true>(q, mw.bg_n, bm, br);
+                        if (mw.refresh(a.cfg, delta)) {  // metrics.py:181-184
+                            if (lane < d) var = fr / mw.fg_n;
                             store_vec(BFHIP_VEC_VAR, var);
                             inv_sd = 1. / LN_SQRTV(var);
                         }
-                        if ((double)delta >= adapt_window) {
-                            fm = bm; fr = br; bm = 0.; br = 0.;
-                            fg_n = bg_n;
-                            bg_n = 10.;
-                            prev_upd = n_samples;
-                            if (a.cfg.doubling) adapt_window *= 2.;
-                        }
-                        n_samples += 1.;
+                        const bool roll = mw.roll(delta);
+                        if (roll) { fm = bm; fr = br; bm = 0.; br = 0.; }
+                        mw.end(a.cfg, roll);
                         if (lane_ok) { WF[lane] = fm; WF[DP + lane] = fr; WF[2 * DP + lane] = bm; WF[3 * DP + lane] = br; }
                         store_vec(BFHIP_VEC_FG_MEAN, fm);
                         store_vec(BFHIP_VEC_FG_RAW, fr);
                         store_vec(BFHIP_VEC_BG_MEAN, bm);
                         store_vec(BFHIP_VEC_BG_RAW, br);
                         if (lane == 0) {
-                            WF[4 * DP + 0] = fg_n; WF[4 * DP + 1] = bg_n; WF[4 * DP + 2] = n_samples; WF[4 * DP + 3] = prev_upd; WF[4 * DP + 4] = adapt_window;
-                            scp[BFHIP_SC_FG_N] = fg_n;
-                            scp[BFHIP_SC_BG_N] = bg_n;
-                            scp[BFHIP_SC_N_SAMPLES] = n_samples;
-                            scp[BFHIP_SC_PREV_UPDATE] = prev_upd;
-                            scp[BFHIP_SC_ADAPT_WINDOW] = adapt_window;
+                            WF[4 * DP + 0] = mw.fg_n; WF[4 * DP + 1] = mw.bg_n; WF[4 * DP + 2] = mw.n_samples; WF[4 * DP + 3] = mw.prev_upd;
+                            WF[4 * DP + 4] = mw.adapt_window;
+                            scp[BFHIP_SC_FG_N] = mw.fg_n;
+                            scp[BFHIP_SC_BG_N] = mw.bg_n;
+                            scp[BFHIP_SC_N_SAMPLES] = mw.n_samples;
+                            scp[BFHIP_SC_PREV_UPDATE] = mw.prev_upd;
+                            scp[BFHIP_SC_ADAPT_WINDOW] = mw.adapt_window;
                         }
                     }
                     i_iter += 1;

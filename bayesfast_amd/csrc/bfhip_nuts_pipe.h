@@ -257,77 +257,50 @@ __global__ __launch_bounds__(1024) void bf_nuts_pipe_kernel(DevModel m, SamplerA
             const double accept_stat = acc_sum / (double)n_prop;  // nuts.py:186
             double log_step = cs_get(CS_LOG_STEP), log_bar = cs_get(CS_LOG_BAR);
             if (warm && a.cfg.adapt_step_size) {  // step_size.py:31-45
-                const double count = cs_get(CS_COUNT);
-                const double wgt = 1. / (count + a.cfg.t_0);
-                const double hbar = ((1. - wgt) * cs_get(CS_HBAR) + wgt * (a.cfg.target_accept - accept_stat));
-                log_step = cs_get(CS_SMU) - hbar * usqrt(count) / a.cfg.gamma;
-                const double mk = uexp(-a.cfg.k * ulog(count));  // count ** -k
-                log_bar = mk * log_step + (1. - mk) * log_bar;
+                double count = cs_get(CS_COUNT), hbar = cs_get(CS_HBAR);
+                BfStepAdapt<true>::step(a.cfg, accept_stat, cs_get(CS_SMU), hbar, log_step, log_bar, count, BfUniMath());
                 cs_set(CS_HBAR, hbar);
                 cs_set(CS_LOG_STEP, log_step);
                 cs_set(CS_LOG_BAR, log_bar);
-                cs_set(CS_COUNT, count + 1.);
+                cs_set(CS_COUNT, count);
                 cs_set(CS_STEP_NOW, uexp(log_step));
                 cs_set(CS_STEP_BAR, uexp(log_bar));
             }
             const double prop_E = cs_get(CS_PROP_E), prop_logp = cs_get(CS_PROP_LOGP);
             const int orow = i_iter - a.iter_out0;
             if (orow >= 0 && orow < a.n_out) {  // (q is the new sample: phase A of this trip took it from the proposal slot)
-                if (lane == 0) {
-                    double *st = a.stats + ((size_t)chain * a.n_out + orow) * BFHIP_STAT_STRIDE;
-                    st[BFHIP_NS_LOGP] = prop_logp;
-                    st[BFHIP_NS_ENERGY] = prop_E;
-                    st[BFHIP_NS_TREE_DEPTH] = (double)depth;
-                    st[BFHIP_NS_TREE_SIZE] = (double)n_prop;
-                    st[BFHIP_NS_MEAN_TREE_ACCEPT] = accept_stat;
-                    st[BFHIP_NS_STEP_SIZE] = cs_get(CS_STEP_NOW);
-                    st[BFHIP_NS_STEP_SIZE_BAR] = cs_get(CS_STEP_BAR);
-                    st[BFHIP_NS_WARMUP] = warm ? 1. : 0.;
-                    st[BFHIP_NS_ENERGY_CHANGE] = prop_E - start_energy;
-                    st[BFHIP_NS_MAX_ENERGY_CHANGE] = max_de;
-                    st[BFHIP_NS_DIVERGING] = (double)diverged;
-                }
+                if (lane == 0)
+                    bf_stats_row_nuts(a.stats + ((size_t)chain * a.n_out + orow) * BFHIP_STAT_STRIDE, prop_logp, prop_E, depth, n_prop,
+                                      accept_stat, cs_get(CS_STEP_NOW), cs_get(CS_STEP_BAR), warm, start_energy, max_de, diverged);
                 double *sp = a.samples + ((size_t)chain * a.n_out + orow) * d;
                 if (lane < d) sp[lane] = q;
             }
-            // QuadMetricDiagAdapt.update: metrics.py:186-211, _WeightedVariance.add_sample :354-360
+            // QuadMetricDiagAdapt.update: metrics.py:186-211
             if (warm && a.cfg.adapt_metric) {
-                double fg_n = rfl(scp[BFHIP_SC_FG_N]), bg_n = rfl(scp[BFHIP_SC_BG_N]);
-                double n_samples = rfl(scp[BFHIP_SC_N_SAMPLES]), prev_upd = rfl(scp[BFHIP_SC_PREV_UPDATE]);
-                double adapt_window = rfl(scp[BFHIP_SC_ADAPT_WINDOW]);
-                const long delta = (long)(n_samples - prev_upd);
+                BfMetricWindow mw{rfl(scp[BFHIP_SC_FG_N]), rfl(scp[BFHIP_SC_BG_N]), rfl(scp[BFHIP_SC_N_SAMPLES]),
+                                  rfl(scp[BFHIP_SC_PREV_UPDATE]), rfl(scp[BFHIP_SC_ADAPT_WINDOW])};
+                const long delta = mw.begin();
                 double fm = load_vec(BFHIP_VEC_FG_MEAN, 0.), fr = load_vec(BFHIP_VEC_FG_RAW, 0.);
                 double bm = load_vec(BFHIP_VEC_BG_MEAN, 0.), br = load_vec(BFHIP_VEC_BG_RAW, 0.);
-                fg_n += 1.;
-                bg_n += 1.;
-                double od = q - fm;
-                fm += od / fg_n;
-                fr += 1. * od * (q - fm);
-                od = q - bm;
-                bm += od / bg_n;
-                br += 1. * od * (q - bm);
-                if ((delta + 1) % (long)a.cfg.update_window == 0) {  // metrics.py:181-184
-                    if (lane < d) var = fr / fg_n;
+                bf_welford_add<true>(q, mw.fg_n, fm, fr);
+                bf_welford_add<true>(q, mw.bg_n, bm, br);
+                if (mw.refresh(a.cfg, delta)) {  // metrics.py:181-184
+                    if (lane < d) var = fr / mw.fg_n;
                     store_vec(BFHIP_VEC_VAR, var);
                 }
-                if ((double)delta >= adapt_window) {
-                    fm = bm; fr = br; bm = 0.; br = 0.;
-                    fg_n = bg_n;
-                    bg_n = 10.;
-                    prev_upd = n_samples;
-                    if (a.cfg.doubling) adapt_window *= 2.;
-                }
-                n_samples += 1.;
+                const bool roll = mw.roll(delta);
+                if (roll) { fm = bm; fr = br; bm = 0.; br = 0.; }
+                mw.end(a.cfg, roll);
                 store_vec(BFHIP_VEC_FG_MEAN, fm);
                 store_vec(BFHIP_VEC_FG_RAW, fr);
                 store_vec(BFHIP_VEC_BG_MEAN, bm);
                 store_vec(BFHIP_VEC_BG_RAW, br);
                 if (lane == 0) {
-                    scp[BFHIP_SC_FG_N] = fg_n;
-                    scp[BFHIP_SC_BG_N] = bg_n;
-                    scp[BFHIP_SC_N_SAMPLES] = n_samples;
-                    scp[BFHIP_SC_PREV_UPDATE] = prev_upd;
-                    scp[BFHIP_SC_ADAPT_WINDOW] = adapt_window;
+                    scp[BFHIP_SC_FG_N] = mw.fg_n;
+                    scp[BFHIP_SC_BG_N] = mw.bg_n;
+                    scp[BFHIP_SC_N_SAMPLES] = mw.n_samples;
+                    scp[BFHIP_SC_PREV_UPDATE] = mw.prev_upd;
+                    scp[BFHIP_SC_ADAPT_WINDOW] = mw.adapt_window;
                 }
             }
             i_iter += 1;

@@ -60,6 +60,14 @@ __device__ __attribute__((noinline)) static void bf_sincospi_ni(double x, double
 #include "bfhip_sampler_defs.h"
 
 #include "bfhip_wave.h"
+#include "bfhip_adapt.h"
+
+// math policy of the iteration end (bfhip_adapt.h) in the sliced and pipelined kernels: the out-of-line libm, wave-uniform
+struct BfUniMath {
+    static __device__ __forceinline__ double ex(double x) { return uexp(x); }
+    static __device__ __forceinline__ double lg(double x) { return ulog(x); }
+    static __device__ __forceinline__ double sq(double x) { return usqrt(x); }
+};
 
 template <int W>
 struct SamplerGeo {
@@ -651,16 +659,12 @@ __global__ __launch_bounds__(BF_SAMPLER_WAVES(W, FULLM, FS) * 64) void bf_sample
             const double accept_stat = NUTS ? acc_sum / (double)n_prop : cs_get(CS_HACC);  // nuts.py:186
             double log_step = cs_get(CS_LOG_STEP), log_bar = cs_get(CS_LOG_BAR);
             if (warm && a.cfg.adapt_step_size) {  // step_size.py:31-45
-                const double count = cs_get(CS_COUNT);
-                const double wgt = 1. / (count + a.cfg.t_0);
-                const double hbar = ((1. - wgt) * cs_get(CS_HBAR) + wgt * (a.cfg.target_accept - accept_stat));
-                log_step = cs_get(CS_SMU) - hbar * usqrt(count) / a.cfg.gamma;
-                const double mk = uexp(-a.cfg.k * ulog(count));  // count ** -k
-                log_bar = mk * log_step + (1. - mk) * log_bar;
+                double count = cs_get(CS_COUNT), hbar = cs_get(CS_HBAR);
+                BfStepAdapt<true>::step(a.cfg, accept_stat, cs_get(CS_SMU), hbar, log_step, log_bar, count, BfUniMath());
                 cs_set(CS_HBAR, hbar);
                 cs_set(CS_LOG_STEP, log_step);
                 cs_set(CS_LOG_BAR, log_bar);
-                cs_set(CS_COUNT, count + 1.);
+                cs_set(CS_COUNT, count);
                 cs_set(CS_STEP_NOW, uexp(log_step));
                 cs_set(CS_STEP_BAR, uexp(log_bar));
             }
@@ -668,31 +672,12 @@ __global__ __launch_bounds__(BF_SAMPLER_WAVES(W, FULLM, FS) * 64) void bf_sample
             const int orow = i_iter - a.iter_out0;
             if (orow >= 0 && orow < a.n_out && lane == 0) {
                 double *st = a.stats + ((size_t)chain * a.n_out + orow) * BFHIP_STAT_STRIDE;
-                if (NUTS) {
-                    st[BFHIP_NS_LOGP] = prop_logp;
-                    st[BFHIP_NS_ENERGY] = prop_E;
-                    st[BFHIP_NS_TREE_DEPTH] = (double)depth;
-                    st[BFHIP_NS_TREE_SIZE] = (double)n_prop;
-                    st[BFHIP_NS_MEAN_TREE_ACCEPT] = accept_stat;
-                    st[BFHIP_NS_STEP_SIZE] = cs_get(CS_STEP_NOW);
-                    st[BFHIP_NS_STEP_SIZE_BAR] = cs_get(CS_STEP_BAR);
-                    st[BFHIP_NS_WARMUP] = warm ? 1. : 0.;
-                    st[BFHIP_NS_ENERGY_CHANGE] = prop_E - start_energy;
-                    st[BFHIP_NS_MAX_ENERGY_CHANGE] = max_de;
-                    st[BFHIP_NS_DIVERGING] = (double)diverged;
-                } else {
-                    st[BFHIP_HS_LOGP] = prop_logp;
-                    st[BFHIP_HS_ENERGY] = prop_E;
-                    st[BFHIP_HS_N_INT_STEP] = (double)a.cfg.n_int_step;
-                    st[BFHIP_HS_ACCEPT_STAT] = accept_stat;
-                    st[BFHIP_HS_ACCEPTED] = (double)h_accepted;
-                    st[BFHIP_HS_STEP_SIZE] = cs_get(CS_STEP_NOW);
-                    st[BFHIP_HS_STEP_SIZE_BAR] = cs_get(CS_STEP_BAR);
-                    st[BFHIP_HS_WARMUP] = warm ? 1. : 0.;
-                    st[BFHIP_HS_ENERGY_CHANGE] = cs_get(CS_HDE);
-                    st[BFHIP_HS_DIVERGING] = (double)diverged;
-                    st[10] = 0.;
-                }
+                if (NUTS)
+                    bf_stats_row_nuts(st, prop_logp, prop_E, depth, n_prop, accept_stat, cs_get(CS_STEP_NOW), cs_get(CS_STEP_BAR), warm,
+                                      start_energy, max_de, diverged);
+                else
+                    bf_stats_row_hmc(st, prop_logp, prop_E, a.cfg.n_int_step, accept_stat, h_accepted, cs_get(CS_STEP_NOW),
+                                     cs_get(CS_STEP_BAR), warm, cs_get(CS_HDE), diverged);
             }
             ldv(SL_PROP_Q, PF0);
             unit = U_END2;
@@ -710,29 +695,27 @@ __global__ __launch_bounds__(BF_SAMPLER_WAVES(W, FULLM, FS) * 64) void bf_sample
             }
             if (FULLM && warm && a.cfg.adapt_metric) {
                 // QuadMetricFullAdapt.update: metrics.py:294-324, _WeightedCovariance.add_sample :401-407
-                double fg_n = rfl(scp[BFHIP_SC_FG_N]), bg_n = rfl(scp[BFHIP_SC_BG_N]);
-                double n_samples = rfl(scp[BFHIP_SC_N_SAMPLES]), prev_upd = rfl(scp[BFHIP_SC_PREV_UPDATE]);
-                double adapt_window = rfl(scp[BFHIP_SC_ADAPT_WINDOW]);
-                const long delta = (long)(n_samples - prev_upd);
+                BfMetricWindow mw{rfl(scp[BFHIP_SC_FG_N]), rfl(scp[BFHIP_SC_BG_N]), rfl(scp[BFHIP_SC_N_SAMPLES]),
+                                  rfl(scp[BFHIP_SC_PREV_UPDATE]), rfl(scp[BFHIP_SC_ADAPT_WINDOW])};
+                const long delta = mw.begin();
                 double fm[E], bm[E], od[E], nd[E];
                 load_vec(BFHIP_VEC_FG_MEAN, fm, 0.);
                 load_vec(BFHIP_VEC_BG_MEAN, bm, 0.);
                 double *fgT = matp + BF_MAT_FG * msz, *bgT = matp + BF_MAT_BG * msz, *covT = matp + BF_MAT_COV * msz;
-                fg_n += 1.;
 #pragma unroll
-                for (int e = 0; e < E; ++e) { od[e] = q[e] - fm[e]; fm[e] += od[e] / fg_n; nd[e] = q[e] - fm[e]; }
-                const bool refresh = (delta + 1) % (long)a.cfg.update_window == 0;   // _update_from_weightvar: :287-292
-                bf_welford_cov<E>(fgT, nd, od, d, lane, refresh ? covT : nullptr, fg_n);
-                bg_n += 1.;
+                for (int e = 0; e < E; ++e) { od[e] = q[e] - fm[e]; fm[e] += od[e] / mw.fg_n; nd[e] = q[e] - fm[e]; }
+                const bool refresh = mw.refresh(a.cfg, delta);   // _update_from_weightvar: :287-292
+                bf_welford_cov<E>(fgT, nd, od, d, lane, refresh ? covT : nullptr, mw.fg_n);
 #pragma unroll
-                for (int e = 0; e < E; ++e) { od[e] = q[e] - bm[e]; bm[e] += od[e] / bg_n; nd[e] = q[e] - bm[e]; }
+                for (int e = 0; e < E; ++e) { od[e] = q[e] - bm[e]; bm[e] += od[e] / mw.bg_n; nd[e] = q[e] - bm[e]; }
                 bf_welford_cov<E>(bgT, nd, od, d, lane);
                 if (refresh) {  // (covT = fgT / fg_n was written by the foreground update above)
                     double *wT = matp + BF_MAT_WORK * msz;
                     if (bf_chol_rows<E>(covT, wT, d, lane))
                         bf_chol_publish<E>(wT, matp + BF_MAT_CHOL * msz, matp + BF_MAT_CHOL_ROWS * msz, d, lane);
                 }
-                if ((double)delta >= adapt_window) {
+                const bool roll = mw.roll(delta);
+                if (roll) {
                     for (int j = 0; j < d; ++j) {
 #pragma unroll
                         for (int e = 0; e < E; ++e) {
@@ -745,69 +728,55 @@ __global__ __launch_bounds__(BF_SAMPLER_WAVES(W, FULLM, FS) * 64) void bf_sample
                     }
 #pragma unroll
                     for (int e = 0; e < E; ++e) { fm[e] = bm[e]; bm[e] = 0.; }
-                    fg_n = bg_n;
-                    bg_n = 10.;
-                    prev_upd = n_samples;
-                    if (a.cfg.doubling) adapt_window *= 2.;
                 }
-                n_samples += 1.;
+                mw.end(a.cfg, roll);
                 store_vec(BFHIP_VEC_FG_MEAN, fm);
                 store_vec(BFHIP_VEC_BG_MEAN, bm);
                 if (lane == 0) {
-                    scp[BFHIP_SC_FG_N] = fg_n;
-                    scp[BFHIP_SC_BG_N] = bg_n;
-                    scp[BFHIP_SC_N_SAMPLES] = n_samples;
-                    scp[BFHIP_SC_PREV_UPDATE] = prev_upd;
-                    scp[BFHIP_SC_ADAPT_WINDOW] = adapt_window;
+                    scp[BFHIP_SC_FG_N] = mw.fg_n;
+                    scp[BFHIP_SC_BG_N] = mw.bg_n;
+                    scp[BFHIP_SC_N_SAMPLES] = mw.n_samples;
+                    scp[BFHIP_SC_PREV_UPDATE] = mw.prev_upd;
+                    scp[BFHIP_SC_ADAPT_WINDOW] = mw.adapt_window;
                 }
             }
-            // QuadMetricDiagAdapt.update: metrics.py:186-211, _WeightedVariance.add_sample :354-360
+            // QuadMetricDiagAdapt.update: metrics.py:186-211
             if (!FULLM && warm && a.cfg.adapt_metric) {
-                double fg_n = rfl(scp[BFHIP_SC_FG_N]), bg_n = rfl(scp[BFHIP_SC_BG_N]);
-                double n_samples = rfl(scp[BFHIP_SC_N_SAMPLES]), prev_upd = rfl(scp[BFHIP_SC_PREV_UPDATE]);
-                double adapt_window = rfl(scp[BFHIP_SC_ADAPT_WINDOW]);
-                const long delta = (long)(n_samples - prev_upd);
+                BfMetricWindow mw{rfl(scp[BFHIP_SC_FG_N]), rfl(scp[BFHIP_SC_BG_N]), rfl(scp[BFHIP_SC_N_SAMPLES]),
+                                  rfl(scp[BFHIP_SC_PREV_UPDATE]), rfl(scp[BFHIP_SC_ADAPT_WINDOW])};
+                const long delta = mw.begin();
                 double fm[E], fr[E], bm[E], br[E];
                 load_vec(BFHIP_VEC_FG_MEAN, fm, 0.);
                 load_vec(BFHIP_VEC_FG_RAW, fr, 0.);
                 load_vec(BFHIP_VEC_BG_MEAN, bm, 0.);
                 load_vec(BFHIP_VEC_BG_RAW, br, 0.);
-                fg_n += 1.;
-                bg_n += 1.;
 #pragma unroll
                 for (int e = 0; e < E; ++e) {
-                    double od = q[e] - fm[e];
-                    fm[e] += od / fg_n;
-                    fr[e] += 1. * od * (q[e] - fm[e]);
-                    od = q[e] - bm[e];
-                    bm[e] += od / bg_n;
-                    br[e] += 1. * od * (q[e] - bm[e]);
+                    bf_welford_add<true>(q[e], mw.fg_n, fm[e], fr[e]);
+                    bf_welford_add<true>(q[e], mw.bg_n, bm[e], br[e]);
                 }
-                if ((delta + 1) % (long)a.cfg.update_window == 0) {  // metrics.py:181-184
+                if (mw.refresh(a.cfg, delta)) {  // metrics.py:181-184
 #pragma unroll
                     for (int e = 0; e < E; ++e)
-                        if (lane * E + e < d) var[e] = fr[e] / fg_n;
+                        if (lane * E + e < d) var[e] = fr[e] / mw.fg_n;
                     store_vec(BFHIP_VEC_VAR, var);
                 }
-                if ((double)delta >= adapt_window) {
+                const bool roll = mw.roll(delta);
+                if (roll) {
 #pragma unroll
                     for (int e = 0; e < E; ++e) { fm[e] = bm[e]; fr[e] = br[e]; bm[e] = 0.; br[e] = 0.; }
-                    fg_n = bg_n;
-                    bg_n = 10.;
-                    prev_upd = n_samples;
-                    if (a.cfg.doubling) adapt_window *= 2.;
                 }
-                n_samples += 1.;
+                mw.end(a.cfg, roll);
                 store_vec(BFHIP_VEC_FG_MEAN, fm);
                 store_vec(BFHIP_VEC_FG_RAW, fr);
                 store_vec(BFHIP_VEC_BG_MEAN, bm);
                 store_vec(BFHIP_VEC_BG_RAW, br);
                 if (lane == 0) {
-                    scp[BFHIP_SC_FG_N] = fg_n;
-                    scp[BFHIP_SC_BG_N] = bg_n;
-                    scp[BFHIP_SC_N_SAMPLES] = n_samples;
-                    scp[BFHIP_SC_PREV_UPDATE] = prev_upd;
-                    scp[BFHIP_SC_ADAPT_WINDOW] = adapt_window;
+                    scp[BFHIP_SC_FG_N] = mw.fg_n;
+                    scp[BFHIP_SC_BG_N] = mw.bg_n;
+                    scp[BFHIP_SC_N_SAMPLES] = mw.n_samples;
+                    scp[BFHIP_SC_PREV_UPDATE] = mw.prev_upd;
+                    scp[BFHIP_SC_ADAPT_WINDOW] = mw.adapt_window;
                 }
             }
             i_iter += 1;

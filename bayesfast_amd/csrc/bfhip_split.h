@@ -953,77 +953,51 @@ BF_DEV void bf_split_body(const DevModel &m, const SamplerArgs &a, double *lds) 
                 const double *cr = cold(i_iter);
                 double log_step = cr[K_LOG_STEP * 16], log_bar = cr[K_LOG_BAR * 16], hbar = cr[K_HBAR * 16], count = cr[K_COUNT * 16];
                 const double smu = cr[K_SMU * 16];
-                double fg_n = cr[K_FG_N * 16], bg_n = cr[K_BG_N * 16], n_samples = cr[K_N_SAMPLES * 16], prev_upd = cr[K_PREV_UPD * 16];
-                double adapt_window = cr[K_ADAPT_WINDOW * 16];
+                BfMetricWindow mw{cr[K_FG_N * 16], cr[K_BG_N * 16], cr[K_N_SAMPLES * 16], cr[K_PREV_UPD * 16], cr[K_ADAPT_WINDOW * 16]};
                 double step_now = cr[K_STEP_NOW * 16], step_bar = cr[K_STEP_BAR * 16];
                 if (warm && a.cfg.adapt_step_size) {  // step_size.py:31-45
-                    const double wgt = 1. / (count + a.cfg.t_0);
-                    hbar = ((1. - wgt) * hbar + wgt * (a.cfg.target_accept - accept_stat));
-                    log_step = smu - hbar * bf_sqrt(count) / a.cfg.gamma;
-                    const double mk = bf_exp(-a.cfg.k * bf_log(count));  // count ** -k
-                    log_bar = mk * log_step + (1. - mk) * log_bar;
-                    count = count + 1.;
+                    BfStepAdapt<false>::step(a.cfg, accept_stat, smu, hbar, log_step, log_bar, count, BfLaneMath());
                     step_now = bf_exp(log_step);
                     step_bar = bf_exp(log_bar);
                 }
                 // the proposal (PRq, PRg) is the new sample and the start of the next iteration
                 const int orow = i_iter - a.iter_out0;
                 if (orow >= 0 && orow < a.n_out) {
-                    if (writer) {
-                        double *sp = a.stats + ((size_t)chain * a.n_out + orow) * BFHIP_STAT_STRIDE;
-                        sp[BFHIP_NS_LOGP] = prop_logp;
-                        sp[BFHIP_NS_ENERGY] = prop_E;
-                        sp[BFHIP_NS_TREE_DEPTH] = (double)depth;
-                        sp[BFHIP_NS_TREE_SIZE] = (double)n_prop;
-                        sp[BFHIP_NS_MEAN_TREE_ACCEPT] = accept_stat;
-                        sp[BFHIP_NS_STEP_SIZE] = step_now;
-                        sp[BFHIP_NS_STEP_SIZE_BAR] = step_bar;
-                        sp[BFHIP_NS_WARMUP] = warm ? 1. : 0.;
-                        sp[BFHIP_NS_ENERGY_CHANGE] = prop_E - start_energy;
-                        sp[BFHIP_NS_MAX_ENERGY_CHANGE] = max_de;
-                        sp[BFHIP_NS_DIVERGING] = (double)diverged;
-                    }
+                    if (writer)
+                        bf_stats_row_nuts(a.stats + ((size_t)chain * a.n_out + orow) * BFHIP_STAT_STRIDE, prop_logp, prop_E, depth, n_prop,
+                                          accept_stat, step_now, step_bar, warm, start_energy, max_de, diverged);
                     double *xp = a.samples + ((size_t)chain * a.n_out + orow) * d;
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         if (dbase + 4 * r < d) xp[dbase + 4 * r] = PRq[r];
                 }
                 bool var_changed = false;
-                // QuadMetricDiagAdapt.update: metrics.py:186-211, _WeightedVariance.add_sample :354-360
+                // QuadMetricDiagAdapt.update: metrics.py:186-211
                 if (warm && a.cfg.adapt_metric) {
-                    const long delta = (long)(n_samples - prev_upd);
+                    const long delta = mw.begin();
                     double fm[4], fr[4], bm[4], br[4];
                     load_vec(BFHIP_VEC_FG_MEAN, fm, 0.);
                     load_vec(BFHIP_VEC_FG_RAW, fr, 0.);
                     load_vec(BFHIP_VEC_BG_MEAN, bm, 0.);
                     load_vec(BFHIP_VEC_BG_RAW, br, 0.);
-                    fg_n += 1.;
-                    bg_n += 1.;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        double od = PRq[r] - fm[r];
-                        fm[r] += od / fg_n;
-                        fr[r] += 1. * od * (PRq[r] - fm[r]);
-                        od = PRq[r] - bm[r];
-                        bm[r] += od / bg_n;
-                        br[r] += 1. * od * (PRq[r] - bm[r]);
+                        bf_welford_add<false>(PRq[r], mw.fg_n, fm[r], fr[r]);
+                        bf_welford_add<false>(PRq[r], mw.bg_n, bm[r], br[r]);
                     }
-                    if ((delta + 1) % (long)a.cfg.update_window == 0) {  // metrics.py:181-184
+                    if (mw.refresh(a.cfg, delta)) {  // metrics.py:181-184
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            if (dbase + 4 * r < d) var[r] = fr[r] / fg_n;
+                            if (dbase + 4 * r < d) var[r] = fr[r] / mw.fg_n;
                         store_vec(BFHIP_VEC_VAR, var);
                         var_changed = true;
                     }
-                    if ((double)delta >= adapt_window) {
+                    const bool roll = mw.roll(delta);
+                    if (roll) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) { fm[r] = bm[r]; fr[r] = br[r]; bm[r] = 0.; br[r] = 0.; }
-                        fg_n = bg_n;
-                        bg_n = 10.;
-                        prev_upd = n_samples;
-                        if (a.cfg.doubling) adapt_window *= 2.;
                     }
-                    n_samples += 1.;
+                    mw.end(a.cfg, roll);
                     store_vec(BFHIP_VEC_FG_MEAN, fm);
                     store_vec(BFHIP_VEC_FG_RAW, fr);
                     store_vec(BFHIP_VEC_BG_MEAN, bm);
@@ -1033,8 +1007,8 @@ BF_DEV void bf_split_body(const DevModel &m, const SamplerArgs &a, double *lds) 
                 {
                     double *cw = cold(i_iter);
                     cw[K_LOG_STEP * 16] = log_step; cw[K_LOG_BAR * 16] = log_bar; cw[K_HBAR * 16] = hbar; cw[K_SMU * 16] = smu;
-                    cw[K_COUNT * 16] = count; cw[K_FG_N * 16] = fg_n; cw[K_BG_N * 16] = bg_n; cw[K_N_SAMPLES * 16] = n_samples;
-                    cw[K_PREV_UPD * 16] = prev_upd; cw[K_ADAPT_WINDOW * 16] = adapt_window;
+                    cw[K_COUNT * 16] = count; cw[K_FG_N * 16] = mw.fg_n; cw[K_BG_N * 16] = mw.bg_n; cw[K_N_SAMPLES * 16] = mw.n_samples;
+                    cw[K_PREV_UPD * 16] = mw.prev_upd; cw[K_ADAPT_WINDOW * 16] = mw.adapt_window;
                     cw[K_STEP_NOW * 16] = step_now; cw[K_STEP_BAR * 16] = step_bar;
                 }
                 if (i_iter < a.iter_end) {

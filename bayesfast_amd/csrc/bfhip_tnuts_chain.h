@@ -15,6 +15,7 @@
 #include "bfhip_sampler_defs.h"
 #include "bfhip_wave.h"
 #include "bfhip_metric.h"
+#include "bfhip_adapt.h"
 #include "bfhip_tnuts.h"
 
 // The velocity M^-1 p of a state: kept with the state under the full-rank metric (a matrix-vector product), recomputed as
@@ -77,8 +78,8 @@ __device__ __forceinline__ void tn_run_chain(const TnutsArgs &a, const int chain
     double log_step = scp[BFHIP_SC_LOG_STEP], log_bar = scp[BFHIP_SC_LOG_BAR], hbar = scp[BFHIP_SC_HBAR];
     const double smu = scp[BFHIP_SC_MU];
     double count = scp[BFHIP_SC_COUNT];
-    double fg_n = scp[BFHIP_SC_FG_N], bg_n = scp[BFHIP_SC_BG_N], n_samples = scp[BFHIP_SC_N_SAMPLES];
-    double prev_upd = scp[BFHIP_SC_PREV_UPDATE], adapt_window = scp[BFHIP_SC_ADAPT_WINDOW];
+    BfMetricWindow mw{scp[BFHIP_SC_FG_N], scp[BFHIP_SC_BG_N], scp[BFHIP_SC_N_SAMPLES], scp[BFHIP_SC_PREV_UPDATE],
+                      scp[BFHIP_SC_ADAPT_WINDOW]};
     int i_iter = (int)scp[BFHIP_SC_I_ITER], err = (int)scp[BFHIP_SC_ERROR];
     double qc[E], var[E];
     auto load_vec = [&](int field, double (&v)[E], double pad) {
@@ -351,7 +352,9 @@ __device__ __forceinline__ void tn_run_chain(const TnutsArgs &a, const int chain
         if (err) break;
         // ---- iteration end: base_hmc.py:252-262 ----
         const double accept_stat = accept_sum / (double)n_prop;
-        if (warm && a.cfg.adapt_step_size) {  // step_size.py:31-45
+        // step_size.py:31-45.  (This driver's own copy, NOT BfStepAdapt of bfhip_adapt.h: left to the compiler, the tempered kernels' build
+        // fuses the product with the OLD term of each sum -- fma(1 - w, hbar, w (target - accept)) --, neither of the helper's forms.)
+        if (warm && a.cfg.adapt_step_size) {
             const double wgt = 1. / (count + a.cfg.t_0);
             hbar = ((1. - wgt) * hbar + wgt * (a.cfg.target_accept - accept_stat));
             log_step = smu - hbar * sqrt(count) / a.cfg.gamma;
@@ -364,18 +367,8 @@ __device__ __forceinline__ void tn_run_chain(const TnutsArgs &a, const int chain
         const int orow = i_iter - a.iter_out0;
         if (orow >= 0 && orow < a.n_out) {
             if (lane == 0) {
-                double *st = a.stats + ((size_t)chain * a.n_out + orow) * BFHIP_STAT_STRIDE;
-                st[BFHIP_NS_LOGP] = prop_logp;
-                st[BFHIP_NS_ENERGY] = prop_E;
-                st[BFHIP_NS_TREE_DEPTH] = (double)depth;
-                st[BFHIP_NS_TREE_SIZE] = (double)n_prop;
-                st[BFHIP_NS_MEAN_TREE_ACCEPT] = accept_stat;
-                st[BFHIP_NS_STEP_SIZE] = exp(log_step);
-                st[BFHIP_NS_STEP_SIZE_BAR] = exp(log_bar);
-                st[BFHIP_NS_WARMUP] = warm ? 1. : 0.;
-                st[BFHIP_NS_ENERGY_CHANGE] = prop_E - start.energy;
-                st[BFHIP_NS_MAX_ENERGY_CHANGE] = max_de;
-                st[BFHIP_NS_DIVERGING] = (double)diverging;
+                bf_stats_row_nuts(a.stats + ((size_t)chain * a.n_out + orow) * BFHIP_STAT_STRIDE, prop_logp, prop_E, depth, n_prop, accept_stat,
+                                  exp(log_step), exp(log_bar), warm, start.energy, max_de, diverging);
                 double *tt = a.stats_t + ((size_t)chain * a.n_out + orow) * 2;
                 tt[0] = prop_u;
                 tt[1] = (prop_w == 0) ? 1. : prop_w / expm1(prop_w);
@@ -385,26 +378,25 @@ __device__ __forceinline__ void tn_run_chain(const TnutsArgs &a, const int chain
             });
         }
         if (warm && a.cfg.adapt_metric) {
-            const long delta = (long)(n_samples - prev_upd);
+            const long delta = mw.begin();
+            const bool roll = mw.roll(delta);
             if constexpr (FULLM) {
                 // QuadMetricFullAdapt.update: metrics.py:294-324, _WeightedCovariance.add_sample :401-407 (as in bfhip_sampler.hip)
                 double fm[E], bm[E], od[E], nd[E];
                 load_vec(BFHIP_VEC_FG_MEAN, fm, 0.);
                 load_vec(BFHIP_VEC_BG_MEAN, bm, 0.);
                 double *fgT = matp + BF_MAT_FG * msz, *bgT = matp + BF_MAT_BG * msz, *covT = matp + BF_MAT_COV * msz;
-                fg_n += 1.;
-                tn_each<E>([&](auto e) { od[e] = qc[e] - fm[e]; fm[e] += od[e] / fg_n; nd[e] = qc[e] - fm[e]; });
-                const bool refresh = (delta + 1) % (long)a.cfg.update_window == 0;   // _update_from_weightvar: :287-292
-                bf_welford_cov<E>(fgT, nd, od, d, lane, refresh ? covT : nullptr, fg_n);
-                bg_n += 1.;
-                tn_each<E>([&](auto e) { od[e] = qc[e] - bm[e]; bm[e] += od[e] / bg_n; nd[e] = qc[e] - bm[e]; });
+                tn_each<E>([&](auto e) { od[e] = qc[e] - fm[e]; fm[e] += od[e] / mw.fg_n; nd[e] = qc[e] - fm[e]; });
+                const bool refresh = mw.refresh(a.cfg, delta);   // _update_from_weightvar: :287-292
+                bf_welford_cov<E>(fgT, nd, od, d, lane, refresh ? covT : nullptr, mw.fg_n);
+                tn_each<E>([&](auto e) { od[e] = qc[e] - bm[e]; bm[e] += od[e] / mw.bg_n; nd[e] = qc[e] - bm[e]; });
                 bf_welford_cov<E>(bgT, nd, od, d, lane);
                 if (refresh) {
                     double *wT = matp + BF_MAT_WORK * msz;
                     if (bf_chol_rows<E>(covT, wT, d, lane))
                         bf_chol_publish<E>(wT, matp + BF_MAT_CHOL * msz, matp + BF_MAT_CHOL_ROWS * msz, d, lane);
                 }
-                if ((double)delta >= adapt_window) {
+                if (roll) {
                     for (int j = 0; j < d; ++j) {
                         tn_each<E>([&](auto e) {
                             const int i = lane * E + e;
@@ -415,10 +407,7 @@ __device__ __forceinline__ void tn_run_chain(const TnutsArgs &a, const int chain
                         });
                     }
                     tn_each<E>([&](auto e) { fm[e] = bm[e]; bm[e] = 0.; });
-                    fg_n = bg_n; bg_n = 10.; prev_upd = n_samples;
-                    if (a.cfg.doubling) adapt_window *= 2.;
                 }
-                n_samples += 1.;
                 store_vec(BFHIP_VEC_FG_MEAN, fm);
                 store_vec(BFHIP_VEC_BG_MEAN, bm);
             } else {
@@ -426,26 +415,21 @@ __device__ __forceinline__ void tn_run_chain(const TnutsArgs &a, const int chain
                 double fm[E], fr[E], bm[E], br[E];
                 load_vec(BFHIP_VEC_FG_MEAN, fm, 0.); load_vec(BFHIP_VEC_FG_RAW, fr, 0.);
                 load_vec(BFHIP_VEC_BG_MEAN, bm, 0.); load_vec(BFHIP_VEC_BG_RAW, br, 0.);
-                fg_n += 1.; bg_n += 1.;
                 tn_each<E>([&](auto e) {
-                    double od = qc[e] - fm[e]; fm[e] += od / fg_n; fr[e] += 1. * od * (qc[e] - fm[e]);
-                    od = qc[e] - bm[e]; bm[e] += od / bg_n; br[e] += 1. * od * (qc[e] - bm[e]);
+                    bf_welford_add<true>(qc[e], mw.fg_n, fm[e], fr[e]);
+                    bf_welford_add<true>(qc[e], mw.bg_n, bm[e], br[e]);
                 });
-                if ((delta + 1) % (long)a.cfg.update_window == 0) {
+                if (mw.refresh(a.cfg, delta)) {
                     tn_each<E>([&](auto e) {
-                        if (in[e]) var[e] = fr[e] / fg_n;
+                        if (in[e]) var[e] = fr[e] / mw.fg_n;
                     });
                     store_vec(BFHIP_VEC_VAR, var);
                 }
-                if ((double)delta >= adapt_window) {
-                    tn_each<E>([&](auto e) { fm[e] = bm[e]; fr[e] = br[e]; bm[e] = 0.; br[e] = 0.; });
-                    fg_n = bg_n; bg_n = 10.; prev_upd = n_samples;
-                    if (a.cfg.doubling) adapt_window *= 2.;
-                }
-                n_samples += 1.;
+                if (roll) tn_each<E>([&](auto e) { fm[e] = bm[e]; fr[e] = br[e]; bm[e] = 0.; br[e] = 0.; });
                 store_vec(BFHIP_VEC_FG_MEAN, fm); store_vec(BFHIP_VEC_FG_RAW, fr);
                 store_vec(BFHIP_VEC_BG_MEAN, bm); store_vec(BFHIP_VEC_BG_RAW, br);
             }
+            mw.end(a.cfg, roll);
         }
         i_iter += 1;
     }
@@ -454,8 +438,8 @@ __device__ __forceinline__ void tn_run_chain(const TnutsArgs &a, const int chain
     if (lane == 0) {
         for (int k = 0; k < 4; ++k) a.rng[(size_t)chain * 4 + k] = rs[k];
         scp[BFHIP_SC_LOG_STEP] = log_step; scp[BFHIP_SC_LOG_BAR] = log_bar; scp[BFHIP_SC_HBAR] = hbar; scp[BFHIP_SC_COUNT] = count;
-        scp[BFHIP_SC_FG_N] = fg_n; scp[BFHIP_SC_BG_N] = bg_n; scp[BFHIP_SC_N_SAMPLES] = n_samples;
-        scp[BFHIP_SC_PREV_UPDATE] = prev_upd; scp[BFHIP_SC_ADAPT_WINDOW] = adapt_window;
+        scp[BFHIP_SC_FG_N] = mw.fg_n; scp[BFHIP_SC_BG_N] = mw.bg_n; scp[BFHIP_SC_N_SAMPLES] = mw.n_samples;
+        scp[BFHIP_SC_PREV_UPDATE] = mw.prev_upd; scp[BFHIP_SC_ADAPT_WINDOW] = mw.adapt_window;
         scp[BFHIP_SC_I_ITER] = (double)i_iter; scp[BFHIP_SC_ERROR] = (double)err;
         a.tu[chain] = u_cur;
         if (a.n_leapfrog && nlf) atomicAdd(a.n_leapfrog, nlf);

@@ -1,12 +1,14 @@
 // The per-point arithmetic of bayesfast_amd/csrc/bfhip_hess.h -- the analytic Hessian of the surrogate density and the damped Newton
 // maximiser -- compiled for the host with a team of one thread (BF_HOST_EMU: no barriers), on the tables bf_pack_density builds.
 // TEST INFRASTRUCTURE ONLY: it lets the CPU suite check the formulas against differences of the oracle's gradient.
+// Also the host entry points of two helpers every sampler kernel shares: bfhip_constraint.h and bfhip_adapt.h (end of the file).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 #define BF_HOST_EMU 1
 #include "bfhip_hess.h"
+#include "bfhip_adapt.h"
 #include "bfhip_pack.h"
 
 BfTune &bf_tune() {
@@ -162,6 +164,78 @@ extern "C" int bfhost_constraint(int n, const double *x, int kind, double lo, do
         out[5 * i + 2] = lj;
         out[5 * i + 3] = gj;
         out[5 * i + 4] = lj2;
+    }
+    return 0;
+}
+
+// ---- the iteration end's one helper (bfhip_adapt.h), both rounding policies ----
+namespace {
+struct HostMath {
+    static double ex(double x) { return exp(x); }
+    static double lg(double x) { return log(x); }
+    static double sq(double x) { return sqrt(x); }
+};
+
+template <bool FUSED>
+void step_adapt(const bfhip_sampler_config &cfg, int one_call, int n, const double *accept, double smu, double *state, double *out) {
+    double hbar = state[0], log_step = state[1], log_bar = state[2], count = state[3];
+    for (int i = 0; i < n; ++i) {
+        if (one_call) BfStepAdapt<FUSED>::step(cfg, accept[i], smu, hbar, log_step, log_bar, count, HostMath());
+        else BfStepAdapt<FUSED>::update(cfg, BfStepAdapt<FUSED>::consts(cfg, count, HostMath()), accept[i], smu, hbar, log_step, log_bar, count);
+        out[4 * i + 0] = hbar;
+        out[4 * i + 1] = log_step;
+        out[4 * i + 2] = log_bar;
+        out[4 * i + 3] = count;
+    }
+}
+
+template <bool FUSED>
+void welford(int n, const double *x, double n0, double mean, double raw, double *out) {
+    for (int i = 0; i < n; ++i) {
+        n0 += 1.;
+        bf_welford_add<FUSED>(x[i], n0, mean, raw);
+        out[2 * i + 0] = mean;
+        out[2 * i + 1] = raw;
+    }
+}
+}  // namespace
+
+// n successive dual-averaging updates from state = (hbar, log_step, log_bar, count): out[4 i ..] = the state after update i;
+// one_call: through step(), else through consts() and update()
+extern "C" int bfhost_step_adapt(int fused, int one_call, double target_accept, double gamma, double k, double t_0, int n, const double *accept,
+                                 double smu, double *state, double *out) {
+    bfhip_sampler_config cfg;
+    memset(&cfg, 0, sizeof(cfg));
+    cfg.target_accept = target_accept;
+    cfg.gamma = gamma;
+    cfg.k = k;
+    cfg.t_0 = t_0;
+    if (fused) step_adapt<true>(cfg, one_call, n, accept, smu, state, out);
+    else step_adapt<false>(cfg, one_call, n, accept, smu, state, out);
+    return 0;
+}
+
+// n samples added to one element of a Welford window that starts at (n0, mean, raw): out[2 i ..] = mean, raw after sample i
+extern "C" int bfhost_welford(int fused, int n, const double *x, double n0, double mean, double raw, double *out) {
+    if (fused) welford<true>(n, x, n0, mean, raw, out);
+    else welford<false>(n, x, n0, mean, raw, out);
+    return 0;
+}
+
+// n_iter iterations of the metric's window logic from state = (fg_n, bg_n, n_samples, prev_upd, adapt_window):
+// out[7 i ..] = the five scalars after iteration i, then its refresh and roll flags
+extern "C" int bfhost_metric_window(int update_window, int doubling, int n_iter, const double *state, double *out) {
+    bfhip_sampler_config cfg;
+    memset(&cfg, 0, sizeof(cfg));
+    cfg.update_window = update_window;
+    cfg.doubling = doubling;
+    BfMetricWindow mw{state[0], state[1], state[2], state[3], state[4]};
+    for (int i = 0; i < n_iter; ++i) {
+        const long delta = mw.begin();
+        const bool refresh = mw.refresh(cfg, delta), roll = mw.roll(delta);
+        mw.end(cfg, roll);
+        const double row[7] = {mw.fg_n, mw.bg_n, mw.n_samples, mw.prev_upd, mw.adapt_window, refresh ? 1. : 0., roll ? 1. : 0.};
+        memcpy(out + 7 * i, row, sizeof(row));
     }
     return 0;
 }

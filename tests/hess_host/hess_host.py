@@ -58,3 +58,31 @@ def constraint(x, kind, lo, hi):
     if rc != 0:
         raise RuntimeError('bfhost_constraint failed: %d' % rc)
     return out
+
+
+def step_adapt(fused, accept, smu, state, target_accept, gamma, k, t_0, one_call=True):
+    """accept (n,) -> (n, 4): hbar, log_step, log_bar, count after each of n successive updates of ``BfStepAdapt<fused>``
+    (``bfhip_adapt.h``) from state = (hbar, log_step, log_bar, count); through ``step`` (one_call), or ``consts`` and ``update``."""
+    accept = np.ascontiguousarray(accept, dtype=np.float64).ravel()
+    state = np.ascontiguousarray(state, dtype=np.float64)
+    out = np.empty((accept.size, 4))
+    lib().bfhost_step_adapt(C.c_int(int(bool(fused))), C.c_int(int(bool(one_call))), C.c_double(target_accept), C.c_double(gamma), C.c_double(k), C.c_double(t_0),
+                            C.c_int(accept.size), _p(accept), C.c_double(smu), _p(state), _p(out))
+    return out
+
+
+def welford(fused, x, n0, mean, raw):
+    """x (n,) -> (n, 2): mean, raw after each sample added by ``bf_welford_add<fused>`` to a window that starts at (n0, mean, raw)."""
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    out = np.empty((x.size, 2))
+    lib().bfhost_welford(C.c_int(int(bool(fused))), C.c_int(x.size), _p(x), C.c_double(n0), C.c_double(mean), C.c_double(raw), _p(out))
+    return out
+
+
+def metric_window(state, n_iter, update_window, doubling):
+    """-> (n_iter, 7): fg_n, bg_n, n_samples, prev_upd, adapt_window after each iteration of ``BfMetricWindow``, then its refresh and
+    roll flags."""
+    state = np.ascontiguousarray(state, dtype=np.float64)
+    out = np.empty((n_iter, 7))
+    lib().bfhost_metric_window(C.c_int(int(update_window)), C.c_int(int(bool(doubling))), C.c_int(int(n_iter)), _p(state), _p(out))
+    return out

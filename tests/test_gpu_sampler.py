@@ -519,6 +519,78 @@ def test_split_layout_is_bit_identical_to_group_layout_on_the_device(ctx, d):
             assert np.array_equal(u, v, equal_nan=True) if isinstance(u, np.ndarray) else u == v
 
 
+def _window_run(dens, x0, layout, cuts=(40,), **debug):
+    """5 chains through a warm-up of 30 iterations whose metric window (5 samples, doubling, the metric refreshed every third sample)
+    rolls at samples 5 and 15: samples, statistics, sc, vec, random state"""
+    import torch
+    from bayesfast_amd.chains import DeviceChains
+    from bayesfast_amd import _lib
+    try:
+        for k, v in debug.items():
+            _lib.debug_set(k, v)
+        dc = DeviceChains(dens, x0, seed=11, adapt_window=5)
+        parts = [dc.run(n, 'NUTS', n_warmup=30, update_window=3, doubling=True, launch_iters=None, layout=layout) for n in cuts]
+        kernel = _lib.last_kernel()
+    finally:
+        for k in debug:
+            _lib.debug_set(k, {'lone': 1}.get(k, 0))
+    s, st = (torch.cat([p[i] for p in parts], 1).cpu().numpy() for i in (0, 1))
+    return [s, st] + [t.cpu().numpy() for t in (dc.sc, dc.vec, dc.rng)], kernel
+
+
+def _assert_same_bits(a, b, what):
+    for nm, u, v in zip(('samples', 'stats', 'sc', 'vec', 'rng'), a, b):
+        assert np.array_equal(u, v, equal_nan=True), (what, nm, np.argwhere(~((u == v) | ((u != u) & (v != v))))[:5])
+
+
+@pytest.mark.parametrize('d', [10, 40])
+def test_metric_window_switch_is_bit_identical_across_kernels(ctx, d):
+    """The end of an iteration is one helper (csrc/bfhip_adapt.h) in every kernel; the other cross-kernel tests of this module run the
+    default adaptation window of 60 samples inside a warm-up of 30 and never leave the first window.  Here the window rolls twice
+    (background to foreground, the fresh background's weight of 10, one doubling on top of the first) with refreshes of the metric in
+    between, at one element per lane against the padded tail (W = 1 and W = 4): sliced = pipelined = latency kernel and group = split
+    kernel bit for bit, the two families to the 1e-9 of `_compare_nuts` over its first iterations (which hold the first roll)."""
+    from bayesfast_amd.device import DeviceDensity
+    from bayesfast_amd.workloads import correlated_gaussian_spec
+    from bayesfast_amd import _lib
+    spec, _ = correlated_gaussian_spec(d)
+    dens = DeviceDensity(spec, ctx)
+    x0 = np.random.default_rng(2).normal(size=(5, d))
+    sliced, k_sliced = _window_run(dens, x0, 'wave', no_group=1, no_pipe=1)
+    pipe, k_pipe = _window_run(dens, x0, 'wave', no_group=1, lone=0, wave_cpg=16)
+    lone, k_lone = _window_run(dens, x0, 'wave', no_group=1, lone=2)
+    group, k_group = _window_run(dens, x0, 'group')
+    split, k_split = _window_run(dens, x0, 'split')
+    assert 'bf_sampler_kernel' in k_sliced and 'bf_nuts_pipe_kernel' in k_pipe and 'bf_lone_kernel' in k_lone
+    assert k_group.startswith('bf_group_kernel') and k_split.startswith('bf_split_kernel')
+    sc = {f: sliced[2][:, i] for i, f in enumerate(_lib.SC_FIELDS)}
+    assert np.all(sc['adapt_window'] == 20.) and np.all(sc['prev_update'] == 15.) and np.all(sc['n_samples'] == 30.)
+    assert np.all(sc['fg_n'] == 10. + 24.) and np.all(sc['bg_n'] == 10. + 14.)   # (the windows opened after samples 5 and 15 of 0 .. 29)
+    _assert_same_bits(sliced, pipe, 'sliced / pipelined')
+    _assert_same_bits(pipe, lone, 'pipelined / latency')
+    _assert_same_bits(group, split, 'group / split')
+    assert np.array_equal(group[2][:, _lib.SC_FIELDS.index('adapt_window')], sc['adapt_window'])
+    np.testing.assert_allclose(group[0][:, :8], sliced[0][:, :8], rtol=1e-9, atol=1e-9)
+    for f in ('tree_depth', 'tree_size', 'diverging', 'warmup'):
+        i = _lib.NSTATS.index(f)
+        assert np.array_equal(group[1][:, :8, i], sliced[1][:, :8, i]), f
+
+
+def test_launch_cut_across_a_roll_of_the_metric_window_at_d128(ctx):
+    """bf_sampler_kernel at two elements per lane: 40 iterations in one launch against 24 + 16, the cut between the two rolls."""
+    from bayesfast_amd.device import DeviceDensity
+    from bayesfast_amd.workloads import correlated_gaussian_spec
+    from bayesfast_amd import _lib
+    spec, _ = correlated_gaussian_spec(128)
+    dens = DeviceDensity(spec, ctx)
+    x0 = np.random.default_rng(2).normal(size=(5, 128))
+    one, k_one = _window_run(dens, x0, 'auto')
+    two, k_two = _window_run(dens, x0, 'auto', cuts=(24, 16))
+    assert 'bf_sampler_kernel' in k_one and 'bf_sampler_kernel' in k_two
+    assert np.all(one[2][:, _lib.SC_FIELDS.index('adapt_window')] == 20.)
+    _assert_same_bits(one, two, 'one launch / two launches')
+
+
 def test_config2_fitted_bound_on_surrogate_posterior_moments(ctx):
     """T2 for BASELINE config 2 as it is specified: d = 32, 1024 chains, ``PolyModel('quadratic')`` FITTED on
     2 P Sobol-normal points of the target (P = 561) with its extrapolation bound ON, NUTS defaults (1500 iterations, 500

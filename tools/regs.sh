@@ -1,8 +1,13 @@
 #!/bin/bash
 # register / spill summary of every instantiation of a kernel TU: tools/regs.sh bfhip_group.hip [extra flags]
-cd "$(dirname "$0")/../bayesfast_amd/csrc"
+# Compiled with the flags csrc/Makefile gives THIS translation unit (make -n prints its compile line: -ffp-contract=off for some, not
+# for others), so the table is that of the shipped build.
+cd "$(dirname "$0")/../bayesfast_amd/csrc" || exit 1
 src=$1; shift
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Rpass-analysis=kernel-resource-usage "$@" -c $src -o /tmp/regs_tmp.o 2>&1 | python3 -c "
+cmd=$(make -s -n -B "_obj/${src%.hip}.o" | grep -- " -c $src ")
+[ -n "$cmd" ] || { echo "regs.sh: csrc/Makefile has no compile line for $src" >&2; exit 1; }
+tmp=$(mktemp --suffix=.o)
+$cmd -Rpass-analysis=kernel-resource-usage "$@" -o "$tmp" 2>&1 | python3 -c "
 import sys,re
 name=None; info={}
 for l in sys.stdin:
@@ -14,3 +19,4 @@ for l in sys.stdin:
 print('kernel : VGPR AGPR scratch sgpr_spill vgpr_spill')
 for n,v in info.items(): print(n[:70], v)
 "
+rm -f "$tmp"
