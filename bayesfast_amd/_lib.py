@@ -93,6 +93,8 @@ SYMBOLS = {
     'bfhip_metric_init_full': (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, _vp]),
     'bfhip_polymodel_upload': (C.c_int, [_vp, C.POINTER(PolymodelDesc)]),
     'bfhip_polymodel_eval': (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    'bfhip_polymodel_columns': (C.c_int, [_vp, C.c_int, C.c_long, C.c_long, C.c_long, _vp, C.c_int, C.c_long, _vp, _vp, C.c_int, C.c_int,
+                                          _vp, C.c_long, _vp]),
     'bfhip_chi2_stage': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp]),
     'bfhip_pipeline_upload': (C.c_int, [_vp, C.POINTER(PipelineDesc)]),
     'bfhip_design_block': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int]),

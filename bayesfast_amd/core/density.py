@@ -347,6 +347,12 @@ class Chi2PipelineDensity(SurrogateDensity):
                                              self._logp0, _ptr(lp), _ptr(g)))
         return lp, g
 
+    def predictive(self, x, **kw):
+        """Posterior predictive summaries of the surrogate's outputs at the ORIGINAL-space draws x, a GPU tensor
+        (n_chain, n_draw, d) or (n, d): ``bayesfast_amd.utils.predictive(self, x, **kw)``, a ``Predictive``."""
+        from ..utils.predictive import predictive
+        return predictive(self, x, **kw)
+
     def logp_and_grad(self, x, original_space=True):
         x = np.asarray(x, dtype=np.float64)
         lp, g = self.device().logp_and_grad(x.reshape(-1, self.input_size), original_space)

@@ -256,6 +256,212 @@ extern "C" int bfhip_polymodel_eval(bfhip_ctx *ctx, int n, const double *x, doub
     return bf_set_error(BFHIP_ERR_UNSUPPORTED, "unsupported padded dimension %d", ctx->pm.DP);
 }
 
+// ---- a batch of outputs at draws read in place (bayesfast_amd/utils/predictive.py) -------------------------------------------------
+// Sibling of bf_polymodel_eval_kernel without the Jacobian: the same layout and the same arithmetic per value, repeated here so that
+// the kernel above stays what it is.  What differs is around it:
+//   - the points come from the time-major chain tensor (chain stride ldw, row stride ldr, float64 or float32) with the optional
+//     input map xs = (x - lo) / diff, not from a packed (n, d) array;
+//   - a wave holds N = PcTiles<T>::N 16-point tiles, so S_o staged in LDS (T <= 4) serves 64 N points, not 64; without a Jacobian a
+//     tile keeps its evaluation point only (x - mu and H (x - mu) are dead after the bound test), which is what lets it hold several.
+//     N is set by the registers: xe is 8 T VGPRs per tile, and the instantiation is held to two waves per SIMD (T = 8: one);
+//   - the bound test and beta are per point, once; the outputs go out four at a time, lane (c, g) keeping output b0 + g of point c,
+//     so that a wave's store covers 32 contiguous bytes of each of its 16 rows of out, not one double per row.
+// A value depends on its point and its output only: every sum runs over a point's own dimensions in a fixed order (a column of the
+// MFMA and the four lanes of the point), whichever tile, wave, workgroup or output chunk it falls in.
+//
+// x^T M x of the wave's 16 points, this lane's share (bf_sum_g completes it): the MFMA sequence of bf_matvec_w1 with a row tile's
+// four results multiplied in as they arrive, in the order of `for e: s += x[e] * (M x)[e]`.  Without a Jacobian nothing else reads
+// M x, and not keeping it is what leaves the registers to the tiles.
+template <int T>
+__device__ inline double bf_quadform_w1(const double *Af, const double (&x)[4 * T], int lane) {
+    constexpr int NS = 4 * T;
+    double s = 0.;
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        d4_t acc = {0., 0., 0., 0.};
+#pragma unroll
+        for (int k = 0; k < NS; ++k)
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Af[(t * NS + k) * 64 + lane], x[k], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s += x[4 * t + r] * acc[r];
+    }
+    return s;
+}
+
+#ifndef BF_PC_TILES   // tiles a wave holds at T = 1, 2, 4, 8 (a tuning build overrides it: tools/predictive_rate.py --kernel-only)
+#define BF_PC_TILES 8, 4, 2, 1
+#endif
+template <int T> struct PcTiles {
+    static constexpr int TAB[4] = {BF_PC_TILES};
+    static constexpr int N = TAB[T == 1 ? 0 : T == 2 ? 1 : T == 4 ? 2 : 3];
+    static constexpr int WAVES = T <= 4 ? 2 : 1;                            // waves per SIMD the registers are held to
+};
+
+template <int T>
+__global__ __launch_bounds__(256, PcTiles<T>::WAVES) void bf_polymodel_columns_kernel(PolyDev pm, long n, long n_draw, long ldw, long ldr,
+                                                                  const void *__restrict__ xin, int is_f32,
+                                                                  const double *__restrict__ in_lo, const double *__restrict__ in_diff,
+                                                                  int k0, int nb, double *__restrict__ out, long ldo,
+                                                                  double *__restrict__ beta_out) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    constexpr int E = 4 * T, DP = 16 * T, MAT = DP * DP, NT = PcTiles<T>::N;
+    constexpr bool STAGE = T <= 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = lane & 15, g = lane >> 4;
+    const long tile0 = ((long)blockIdx.x * 4 + wave) * NT;
+    const int d = pm.d;
+    const bool has_cubic = pm.n2 > 0 || pm.n3 > 0;
+    double *xst = lds + (STAGE ? MAT : 0) + wave * NT * 16 * DP;  // this wave's evaluation points, plain layout (cubic configs)
+    double xe[NT][E], beta[NT];
+#pragma unroll
+    for (int u = 0; u < NT; ++u) {
+        const long pt = (tile0 + u) * 16 + c;
+        const bool live = pt < n;
+        const unsigned ch = live ? (unsigned)pt / (unsigned)n_draw : 0u;   // (a live point's index is below 2^31)
+        const long off = (long)ch * ldw + (pt - (long)ch * n_draw) * ldr;
+        if (is_f32) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) xe[u][e] = (live && 4 * e + g < d) ? (double)((const float *)xin)[off + 4 * e + g] : 0.;
+        } else {
+#pragma unroll
+            for (int e = 0; e < E; ++e) xe[u][e] = (live && 4 * e + g < d) ? ((const double *)xin)[off + 4 * e + g] : 0.;
+        }
+        if (in_lo) {  // PolyModel._input_scales: that subtraction and that division; the padded dimensions stay 0
+#pragma unroll
+            for (int e = 0; e < E; ++e)
+                if (live && 4 * e + g < d) xe[u][e] = (xe[u][e] - in_lo[4 * e + g]) / in_diff[4 * e + g];
+        }
+        beta[u] = 0.;
+        if (pm.use_bound) {  // the bound test of PolyModel._fun_and_jac: modules/poly.py:467-469
+            double xm[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) xm[e] = xe[u][e] - pm.mu[4 * e + g];
+            beta[u] = sqrt(bf_sum_g(bf_quadform_w1<T>(pm.Hf, xm, lane)));
+            if (beta[u] > pm.alpha) {  // outside: the point the outputs are evaluated at, in place
+#pragma unroll
+                for (int e = 0; e < E; ++e) xe[u][e] = (pm.alpha * xe[u][e] + (beta[u] - pm.alpha) * pm.mu[4 * e + g]) / beta[u];  // :482
+            }
+        }
+        if (beta_out && live && g == 0 && blockIdx.y == 0) beta_out[pt] = beta[u];
+        if (has_cubic) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) xst[(u * 16 + c) * DP + 4 * e + g] = xe[u][e];
+        }
+    }
+    if (has_cubic) {  // written once, read by this wave only
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    // the batch's outputs in groups of four, the groups split over blockIdx.y as the evaluation's outputs are
+    const int n_grp = (nb + 3) / 4, g_per = (n_grp + gridDim.y - 1) / gridDim.y;
+    const int b_beg = min(nb, (int)blockIdx.y * g_per * 4), b_end = min(nb, b_beg + g_per * 4);
+    for (int b0 = b_beg; b0 < b_end; b0 += 4) {
+        double keep[NT];
+#pragma unroll
+        for (int u = 0; u < NT; ++u) keep[u] = 0.;
+#pragma unroll 1
+        for (int j = 0; j < 4 && b0 + j < b_end; ++j) {
+            const int o = k0 + b0 + j;
+            const double *Sf = pm.Sf + (size_t)o * MAT;
+            if (STAGE && pm.has_quad) {
+                __syncthreads();
+                for (int i = threadIdx.x; i < MAT / 2; i += 256) ((d2_t *)lds)[i] = ((const d2_t *)Sf)[i];
+                __syncthreads();
+                Sf = lds;
+            }
+            const double c0 = pm.c0[o], f_mu = pm.use_bound ? pm.f_mu[o] : 0.;
+            double lin[NT], fcub[NT];
+#pragma unroll
+            for (int u = 0; u < NT; ++u) lin[u] = fcub[u] = 0.;
+#pragma unroll
+            for (int e = 0; e < E; ++e) {  // a coefficient is loaded once for the wave's tiles; each sum runs over e in order
+                const double cl = pm.lin[(size_t)o * DP + 4 * e + g];
+#pragma unroll
+                for (int u = 0; u < NT; ++u) lin[u] += cl * xe[u][e];
+            }
+            if (has_cubic) {  // cubic-2 / cubic-3 configs of this output (modules/_poly.pyx:49-137), compact tables; the points
+                DevModel cm;  // are read from the wave's LDS copy, so one copy of this code serves every tile
+                cm.DP = DP;
+                cm.n2 = pm.n2; cm.n3 = pm.n3;
+                cm.mask2 = pm.mask2; cm.pos2 = pm.pos2; cm.mask3 = pm.mask3; cm.pos3 = pm.pos3;
+                cm.A2 = pm.A2 + (size_t)o * pm.n2 * pm.n2;
+                cm.A2t = pm.A2t + (size_t)o * pm.n2 * pm.n2;
+                cm.T3t = pm.T3t + (size_t)o * pm.n3 * pm.n3 * pm.n3;
+#pragma unroll 1
+                for (int u = 0; u < NT; ++u) {
+                    const double *xp = xst + (u * 16 + c) * DP;
+                    double fs = 0.;
+#pragma unroll
+                    for (int e = 0; e < E; ++e) {
+                        double gc, fc;
+                        bf_cubic_grad(cm, 4 * e + g, xp[4 * e + g], [&](int k) { return xp[k]; }, gc, fc);
+                        fs += fc;
+                    }
+                    fs = bf_sum_g(fs);
+#pragma unroll
+                    for (int v = 0; v < NT; ++v) fcub[v] = v == u ? fs : fcub[v];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < NT; ++u) {
+                const double quad = pm.has_quad ? bf_sum_g(bf_quadform_w1<T>(Sf, xe[u], lane)) : 0.;
+                double fo = ((c0 + bf_sum_g(lin[u])) + 0.5 * quad) + fcub[u];
+                if (pm.use_bound && beta[u] > pm.alpha) fo = (beta[u] * fo - (beta[u] - pm.alpha) * f_mu) / pm.alpha;  // modules/poly.py:484-503
+                if (g == j) keep[u] = fo;
+            }
+        }
+        if (b0 + g < b_end) {
+            const long row0 = tile0 * 16 + c;
+            const long i0 = row0 * ldo + b0 + g, step = 16 * ldo;
+#pragma unroll
+            for (int u = 0; u < NT; ++u)
+                if (row0 + u * 16 < n) out[i0 + u * step] = keep[u];
+        }
+    }
+}
+
+template <int T>
+static int launch_polymodel_columns(bfhip_ctx *ctx, long n, long n_draw, long ldw, long ldr, const void *x, int is_f32,
+                                    const double *in_lo, const double *in_diff, int k0, int nb, double *out, long ldo, double *beta) {
+    auto k = bf_polymodel_columns_kernel<T>;
+    const bool cubic = ctx->pm.n2 > 0 || ctx->pm.n3 > 0;
+    const size_t lds = ((T <= 4 ? (size_t)256 * T * T : 0) + (cubic ? (size_t)4 * PcTiles<T>::N * 16 * 16 * T : 0)) * sizeof(double);
+    if (int rc = bf_set_lds(k, lds)) return rc;
+    const long per = 64L * PcTiles<T>::N, grid = (n + per - 1) / per;
+    long ny = (4L * ctx->n_cu + grid - 1) / grid;  // about four workgroups per CU, as launch_polymodel_eval
+    if (ny > (nb + 3) / 4) ny = (nb + 3) / 4;
+    if (ny < 1) ny = 1;
+    hipLaunchKernelGGL(k, dim3((unsigned)grid, (unsigned)ny), dim3(256), lds, ctx->stream, ctx->pm, n, n_draw, ldw, ldr, x, is_f32, in_lo,
+                       in_diff, k0, nb, out, ldo, beta);
+    BF_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int bfhip_polymodel_columns(bfhip_ctx *ctx, int n_chain, long n_draw, long ldw, long ldr, const void *x, int is_f32,
+                                       long since, const double *in_lo, const double *in_diff, int k0, int nb, double *out, long ldo,
+                                       double *beta) {
+    BfDeviceGuard dev_guard(ctx);
+    if (!ctx || n_chain < 0 || n_draw < 0 || since < 0 || k0 < 0 || nb < 1 || ldo < nb || (in_lo == NULL) != (in_diff == NULL))
+        return bf_set_error(BFHIP_ERR_ARG, "bfhip_polymodel_columns: invalid argument");
+    if (!ctx->has_pm) return bf_set_error(BFHIP_ERR_STATE, "bfhip_polymodel_columns: no polymodel uploaded");
+    if ((long)k0 + nb > ctx->pm.m)
+        return bf_set_error(BFHIP_ERR_ARG, "bfhip_polymodel_columns: outputs %d .. %ld of %d", k0, (long)k0 + nb - 1, ctx->pm.m);
+    if (n_chain == 0 || n_draw == 0) return 0;
+    if (!x || !out || ldr < ctx->pm.d || (n_chain > 1 && ldw < 1))
+        return bf_set_error(BFHIP_ERR_ARG, "bfhip_polymodel_columns: invalid argument (x, out, or a row stride below d = %d)", ctx->pm.d);
+    if (n_draw > 0x7fffffffL / n_chain)
+        return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_polymodel_columns: more than 2^31-1 points");
+    const long n = (long)n_chain * n_draw;
+    const void *x0 = is_f32 ? (const void *)((const float *)x + since * ldr) : (const void *)((const double *)x + since * ldr);
+    switch (ctx->pm.DP / 16) {
+    case 1: return launch_polymodel_columns<1>(ctx, n, n_draw, ldw, ldr, x0, is_f32, in_lo, in_diff, k0, nb, out, ldo, beta);
+    case 2: return launch_polymodel_columns<2>(ctx, n, n_draw, ldw, ldr, x0, is_f32, in_lo, in_diff, k0, nb, out, ldo, beta);
+    case 4: return launch_polymodel_columns<4>(ctx, n, n_draw, ldw, ldr, x0, is_f32, in_lo, in_diff, k0, nb, out, ldo, beta);
+    case 8: return launch_polymodel_columns<8>(ctx, n, n_draw, ldw, ldr, x0, is_f32, in_lo, in_diff, k0, nb, out, ldo, beta);
+    }
+    return bf_set_error(BFHIP_ERR_UNSUPPORTED, "unsupported padded dimension %d", ctx->pm.DP);
+}
+
 
 // ---- chi-square stage of a surrogate pipeline (core/density.py:552-560 chain rule fused with the module) ------------
 // One wave per point: lanes stride over the m outputs for r = prec (f - y) and the value, then over the d inputs for

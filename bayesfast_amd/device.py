@@ -576,3 +576,39 @@ class DevicePolyModel:
         if single:
             return f[0], (j[0] if jac else None)
         return f, j
+
+    def fun_columns(self, x, k0, nb, in_lo=None, in_diff=None, beta=False, out=None):
+        """Outputs k0 .. k0 + nb - 1 at the draws of x, a float64 or float32 device tensor (n_chain, n_draw, d) or (n, d) (one
+        chain) with unit stride along d, read in place (``bfhip_polymodel_columns``: a ``[:, since:]`` view goes in without a
+        copy) -> a float64 tensor (n_chain, n_draw, nb), written into ``out`` when given (its rows may be wider than nb: the
+        other columns are left alone).  ``in_lo``, ``in_diff`` (d,): the model sees (x - in_lo) / in_diff.  ``beta=True``: also the
+        tensor (n_chain, n_draw) of bound radii sqrt((xs - mu)^T H (xs - mu)), 0 for a model without a bound."""
+        torch = _torch()
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise NotImplementedError('fun_columns reads a device tensor in place; there is no host evaluation of a PolyModel.')
+        if x.dim() == 2:
+            x = x[None]
+        if x.dim() != 3 or x.shape[2] != self.d or x.dtype not in (torch.float64, torch.float32) or x.device != self.ctx.device:
+            raise ValueError('x should be a float64 or float32 tensor (n_chain, n_draw, %d) or (n, %d) on the model\'s device.'
+                             % (self.d, self.d))
+        if self.d > 1 and x.stride(2) != 1:
+            raise ValueError('x should have unit stride along its last axis.')
+        if (in_lo is None) != (in_diff is None):
+            raise ValueError('in_lo and in_diff go together.')
+        n_chain, n_draw = int(x.shape[0]), int(x.shape[1])
+        k0, nb = int(k0), int(nb)
+        if out is None:
+            out = self.ctx.empty((n_chain, n_draw, max(nb, 0)))
+        elif (out.dtype != torch.float64 or out.dim() != 3 or tuple(out.shape[:2]) != (n_chain, n_draw) or out.shape[2] < nb or
+              out.device != x.device or (out.shape[2] > 1 and out.stride(2) != 1) or (n_draw > 1 and out.stride(0) != n_draw * out.stride(1))):
+            raise ValueError('out should be a float64 tensor (n_chain, n_draw, >= nb) with evenly spaced rows.')
+        self.upload_if_needed()
+        lo = None if in_lo is None else self.ctx.tensor(in_lo, torch.float64).reshape(self.d)
+        diff = None if in_diff is None else self.ctx.tensor(in_diff, torch.float64).reshape(self.d)
+        bt = self.ctx.empty((n_chain, n_draw)) if beta else None
+        ldo = int(out.stride(1)) if n_draw > 1 or n_chain == 1 else int(out.stride(0))
+        _lib.check(self.ctx._lib.bfhip_polymodel_columns(self.ctx.handle, n_chain, n_draw, int(x.stride(0)), int(x.stride(1)), _ptr(x),
+                                                         int(x.dtype == torch.float32), 0, _ptr(lo), _ptr(diff), k0, nb, _ptr(out),
+                                                         ldo, _ptr(bt)))
+        res = out[:, :, :nb]
+        return (res, bt) if beta else res

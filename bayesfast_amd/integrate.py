@@ -286,6 +286,9 @@ def reference_classes(bayesfast=None):
         def summary(self, *args, **kwargs):
             return self._inner.summary(*args, **kwargs)
 
+        def predictive(self, *args, **kwargs):
+            return self._inner.predictive(*args, **kwargs)
+
         # ---- per-chain traces of the reference's own classes, for _get_step_size / _get_metric / users ----
         @property
         def _sample_traces(self):

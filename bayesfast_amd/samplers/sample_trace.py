@@ -475,6 +475,14 @@ class TraceTuple:
         return weighted_summary(self._diag_input(since_iter, include_warmup, original_space, return_type), log_weights=log_weights,
                                 probs=probs)
 
+    def predictive(self, density, log_weights=None, since_iter=None, include_warmup=False, **kw):
+        """Posterior predictive summaries (``bayesfast_amd.utils.predictive``: a ``Predictive``) of the outputs of ``density``, a
+        ``Chi2PipelineDensity`` (or a multi-output ``PolyModel`` of the original-space inputs), at the original-space draws that
+        ``get(since_iter, include_warmup, flatten=False)`` selects, read where ``sample()`` left them; ``kw`` are ``outputs``,
+        ``probs`` and ``batch_bytes``.  Device parts only; single process only, as ``summary``."""
+        from ..utils.predictive import predictive
+        return predictive(density, self._diag_input(since_iter, include_warmup, True, 'samples'), log_weights=log_weights, **kw)
+
     def _local_samples(self, since_iter, include_warmup, original_space):
         """This rank's chains of what ``get(..., flatten=False)`` selects, as a view of the parts (n_chain_local, n_t, n_d),
         unmaterialised; unlike ``_diag_input`` with any number of ranks: for the statistics that are collectives."""

@@ -3,7 +3,8 @@ from .resample import SystematicResampler
 from .diagnostics import rhat, ess, summary
 from .psis import psis, PSISResult, weighted_summary
 from .marginals import marginals, Marginals
+from .predictive import predictive, Predictive
 from .laplace import Laplace, LaplaceResult, make_positive
 
 __all__ = ['SystematicResampler', 'integrated_time', 'AutocorrError', 'Laplace', 'LaplaceResult', 'make_positive', 'rhat', 'ess', 'summary',
-           'psis', 'PSISResult', 'weighted_summary', 'marginals', 'Marginals']
+           'psis', 'PSISResult', 'weighted_summary', 'marginals', 'Marginals', 'predictive', 'Predictive']

@@ -37,7 +37,9 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_DIM 128         /* input_size limit of the device path */
 #define BFHIP_MAX_TREEDEPTH 12
 
-/* 109: bfhip_lstsq_loo, the leave-one-out validation of the least-squares fit (leverages from the kept factor, held-out residuals,
+/* 110: bfhip_polymodel_columns, a batch of the uploaded polymodel's outputs at draws read in place from the (chain, time, dimension)
+ * tensor, and the bound radius of every draw (the posterior predictive summaries).
+ * 109: bfhip_lstsq_loo, the leave-one-out validation of the least-squares fit (leverages from the kept factor, held-out residuals,
  * per-output sums).
  * 108: bfhip_marg_quantise / _extent / _hist1d / _index / _hist2d / _levels, the marginal posterior histograms and their credible levels
  * (additions only: the number stays).  bfhip_wave_packs_probe; bfhip_psis and bfhip_wstat_columns / _moments / _cumweights / _quantiles, the Pareto-smoothed importance
@@ -304,6 +306,21 @@ int bfhip_polymodel_upload(bfhip_ctx *ctx, const bfhip_polymodel_desc *desc);
 /* f (n,m) and, if jac != NULL, jac (n,m,d) for n points x (n,d); device pointers.  Outside the bound every output
  * is extrapolated linearly from the projected point, PolyModel._fj_bound (modules/poly.py:480-503). */
 int bfhip_polymodel_eval(bfhip_ctx *ctx, int n, const double *x, double *f, double *jac);
+
+/* Outputs k0 .. k0 + nb - 1 of the uploaded polymodel at draws read in place from the time-major sample tensor (no Jacobian):
+ *   point (c, i), c < n_chain, i < n_draw, has the coordinates x[c ldw + (since + i) ldr + j], j < d -- the addressing of
+ *   bfhip_diag_columns (float64, or float32 read as float64 when is_f32; ldr >= d); n = n_chain n_draw <= 2^31 - 1;
+ *   in_lo, in_diff (d) device pointers, both or neither: the model sees xs_j = (x_j - in_lo[j]) / in_diff[j], that subtraction and
+ *   that division in float64;
+ *   out[(c n_draw + i) ldo + b] = output k0 + b at xs as bfhip_polymodel_eval defines it (every config order, the bound test, the
+ *   linear extrapolation from the projected point), b < nb, 1 <= nb, k0 + nb <= m, ldo >= nb; columns nb .. ldo - 1 are not written;
+ *   beta (n) or NULL: beta[c n_draw + i] = sqrt((xs - mu)^T H (xs - mu)) of the uploaded bound, 0 when the model carries none (an
+ *   all-linear model ignores its bound); a point is outside exactly when beta > alpha.
+ * A value depends on its point and its output only: not on k0, nb, ldo, n_chain, the size of the launch or the point's place in its
+ * 16-point tile.  Stream-ordered, no host synchronisation.  BFHIP_ERR_STATE without an uploaded polymodel, BFHIP_ERR_UNSUPPORTED for
+ * n > 2^31 - 1; n_chain = 0 or n_draw = 0 returns 0 without a launch; a refused call leaves the uploaded model usable. */
+int bfhip_polymodel_columns(bfhip_ctx *ctx, int n_chain, long n_draw, long ldw, long ldr, const void *x, int is_f32, long since,
+                            const double *in_lo, const double *in_diff, int k0, int nb, double *out, long ldo, double *beta);
 
 /* Downstream analytic module of a pipeline whose first module is the multi-output surrogate: a Gaussian likelihood
  * (chi-square) of its m outputs, with the pipeline's chain rule (core/density.py:552-560: jac = dot(J_out, J_in)) fused in:
