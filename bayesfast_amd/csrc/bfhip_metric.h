@@ -6,9 +6,26 @@
 // rows of all lanes are one contiguous, coalesced segment and a lane only ever re-reads what it wrote itself;
 // values of other rows travel by v_readlane.  The Cholesky factor also has a row-major copy (for the back
 // substitution of metric.random, which walks rows).  Arithmetic is written with explicit non-fused multiplies and
-// adds in the order of the CPU restatement (oracle/bf_oracle.c), so both sides round identically.
+// adds in the order of the CPU restatement (oracle/bf_oracle.c), so both sides round identically: given the positions a
+// chain visited, its matrices are the restatement's bit for bit (tests/test_gpu_metric_full.py holds them to that).
 #pragma once
 #include "bfhip_common.h"
+
+// One product, sum or difference rounded on its own.  HIP's __dmul_rn / __dadd_rn / __dsub_rn do not say that: they are the plain
+// operators, and the compiler contracted every `__dsub_rn(a, __dmul_rn(b, c))` of this file into one fma (hipcc's default is
+// -ffp-contract=fast-honor-pragmas) -- a factor one ulp off wherever the subtraction cancels.  The pragma is what is honoured.
+__device__ inline double bf_mul_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ inline double bf_add_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ inline double bf_sub_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
 
 enum { BF_MAT_COV = 0, BF_MAT_CHOL, BF_MAT_CHOL_ROWS, BF_MAT_FG, BF_MAT_BG, BF_MAT_WORK, BF_MAT_N };
 static_assert(BF_MAT_N == BFHIP_MAT_N, "include/bfhip.h");
@@ -59,7 +76,7 @@ __device__ inline bool bf_chol_rows(const double *aT, double *lT, int d, int lan
                     if (u < nj) {
                         const double ljk = bf_pick<E>(lb[v], j0 + u);              // L[j0 + u][k + v]
 #pragma unroll
-                        for (int e = 0; e < E; ++e) acc[u][e] = __dsub_rn(acc[u][e], __dmul_rn(lb[v][e], ljk));
+                        for (int e = 0; e < E; ++e) acc[u][e] = bf_sub_rn(acc[u][e], bf_mul_rn(lb[v][e], ljk));
                     }
         }
 #pragma unroll
@@ -70,7 +87,7 @@ __device__ inline bool bf_chol_rows(const double *aT, double *lT, int d, int lan
                 for (int v = 0; v < u; ++v) {   // the block's own finished columns, from registers
                     const double ljk = bf_pick<E>(acc[v], j);                      // L[j][j0 + v]
 #pragma unroll
-                    for (int e = 0; e < E; ++e) acc[u][e] = __dsub_rn(acc[u][e], __dmul_rn(acc[v][e], ljk));
+                    for (int e = 0; e < E; ++e) acc[u][e] = bf_sub_rn(acc[u][e], bf_mul_rn(acc[v][e], ljk));
                 }
                 const double s = bf_pick<E>(acc[u], j);
                 if (!(s > 0.)) return false;
@@ -151,7 +168,7 @@ __device__ inline void bf_velocity_full(const double *covT, const double (&pv)[E
 #pragma unroll
             for (int e = 0; e < E; ++e) {
                 const int i = lane * E + e;
-                if (i < d) out[e] = __dadd_rn(out[e], __dmul_rn(c[u][e], pk));
+                if (i < d) out[e] = bf_add_rn(out[e], bf_mul_rn(c[u][e], pk));
             }
         }
     }
@@ -160,7 +177,7 @@ __device__ inline void bf_velocity_full(const double *covT, const double (&pv)[E
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             const int i = lane * E + e;
-            if (i < d) out[e] = __dadd_rn(out[e], __dmul_rn(covT[(size_t)k * d + i], pk));
+            if (i < d) out[e] = bf_add_rn(out[e], bf_mul_rn(covT[(size_t)k * d + i], pk));
         }
     }
 }
@@ -191,8 +208,8 @@ __device__ inline void bf_velocity_full2(const double *covT, const double (&p0)[
             for (int e = 0; e < E; ++e) {
                 const int i = lane * E + e;
                 if (i < d) {
-                    o0[e] = __dadd_rn(o0[e], __dmul_rn(c[u][e], a0));
-                    o1[e] = __dadd_rn(o1[e], __dmul_rn(c[u][e], a1));
+                    o0[e] = bf_add_rn(o0[e], bf_mul_rn(c[u][e], a0));
+                    o1[e] = bf_add_rn(o1[e], bf_mul_rn(c[u][e], a1));
                 }
             }
         }
@@ -204,8 +221,8 @@ __device__ inline void bf_velocity_full2(const double *covT, const double (&p0)[
             const int i = lane * E + e;
             if (i < d) {
                 const double cv = covT[(size_t)k * d + i];
-                o0[e] = __dadd_rn(o0[e], __dmul_rn(cv, a0));
-                o1[e] = __dadd_rn(o1[e], __dmul_rn(cv, a1));
+                o0[e] = bf_add_rn(o0[e], bf_mul_rn(cv, a0));
+                o1[e] = bf_add_rn(o1[e], bf_mul_rn(cv, a1));
             }
         }
     }
@@ -237,9 +254,9 @@ __device__ inline void bf_velocity_full3(const double *covT, const double (&p0)[
             for (int e = 0; e < E; ++e) {
                 const int i = lane * E + e;
                 if (i < d) {
-                    o0[e] = __dadd_rn(o0[e], __dmul_rn(c[u][e], a0));
-                    o1[e] = __dadd_rn(o1[e], __dmul_rn(c[u][e], a1));
-                    o2[e] = __dadd_rn(o2[e], __dmul_rn(c[u][e], a2));
+                    o0[e] = bf_add_rn(o0[e], bf_mul_rn(c[u][e], a0));
+                    o1[e] = bf_add_rn(o1[e], bf_mul_rn(c[u][e], a1));
+                    o2[e] = bf_add_rn(o2[e], bf_mul_rn(c[u][e], a2));
                 }
             }
         }
@@ -251,9 +268,9 @@ __device__ inline void bf_velocity_full3(const double *covT, const double (&p0)[
             const int i = lane * E + e;
             if (i < d) {
                 const double cv = covT[(size_t)k * d + i];
-                o0[e] = __dadd_rn(o0[e], __dmul_rn(cv, a0));
-                o1[e] = __dadd_rn(o1[e], __dmul_rn(cv, a1));
-                o2[e] = __dadd_rn(o2[e], __dmul_rn(cv, a2));
+                o0[e] = bf_add_rn(o0[e], bf_mul_rn(cv, a0));
+                o1[e] = bf_add_rn(o1[e], bf_mul_rn(cv, a1));
+                o2[e] = bf_add_rn(o2[e], bf_mul_rn(cv, a2));
             }
         }
     }
@@ -281,7 +298,7 @@ __device__ inline void bf_solve_lt(const double *cholR, double (&z)[E], int d, i
 #pragma unroll
             for (int e = 0; e < E; ++e) {
                 const int i = lane * E + e;
-                if (i < jj) z[e] = __dsub_rn(z[e], __dmul_rn(rb[u][e], pj));
+                if (i < jj) z[e] = bf_sub_rn(z[e], bf_mul_rn(rb[u][e], pj));
                 else if (i == jj) z[e] = pj;
             }
         }
@@ -297,7 +314,7 @@ __device__ inline void bf_solve_lt(const double *cholR, double (&z)[E], int d, i
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             const int i = lane * E + e;
-            if (i < j) z[e] = __dsub_rn(z[e], __dmul_rn(row[e], pj));
+            if (i < j) z[e] = bf_sub_rn(z[e], bf_mul_rn(row[e], pj));
             else if (i == j) z[e] = pj;
         }
     }
@@ -327,7 +344,7 @@ __device__ inline void bf_welford_cov(double *rawT, const double (&new_diff)[E],
             for (int e = 0; e < E; ++e) {
                 const int i = lane * E + e;
                 if (i < d) {
-                    const double r = __dadd_rn(rb[u][e], __dmul_rn(__dmul_rn(1., new_diff[e]), oj));
+                    const double r = bf_add_rn(rb[u][e], bf_mul_rn(bf_mul_rn(1., new_diff[e]), oj));
                     rawT[(size_t)(j + u) * d + i] = r;
                     if (scaledT) scaledT[(size_t)(j + u) * d + i] = r / n;
                 }
@@ -340,7 +357,7 @@ __device__ inline void bf_welford_cov(double *rawT, const double (&new_diff)[E],
         for (int e = 0; e < E; ++e) {
             const int i = lane * E + e;
             if (i < d) {
-                const double r = __dadd_rn(rawT[(size_t)j * d + i], __dmul_rn(__dmul_rn(1., new_diff[e]), oj));
+                const double r = bf_add_rn(rawT[(size_t)j * d + i], bf_mul_rn(bf_mul_rn(1., new_diff[e]), oj));
                 rawT[(size_t)j * d + i] = r;
                 if (scaledT) scaledT[(size_t)j * d + i] = r / n;
             }
