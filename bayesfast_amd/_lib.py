@@ -132,7 +132,11 @@ SYMBOLS = {
     'bfhip_wstat_moments': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
     'bfhip_wstat_cumweights': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp]),
     'bfhip_wstat_quantiles': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp]),
-    'bfhip_marg_quantise': (C.c_int, [_vp, C.c_long, _vp, C.c_int, _vp, _vp]),
+    'bfhip_ploo_work_bytes': (C.c_size_t, [C.c_long]),
+    'bfhip_ploo_moments': (C.c_int, [_vp, C.c_long, _vp, C.c_long, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t]),
+    'bfhip_ploo_tail': (C.c_int, [_vp, C.c_long, _vp, C.c_long, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t]),
+    'bfhip_ploo_finish': (C.c_int, [_vp, C.c_long, _vp, C.c_long, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t]),
+    'bfhip_marg_quantise':(C.c_int, [_vp, C.c_long, _vp, C.c_int, _vp, _vp]),
     'bfhip_marg_extent': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
     'bfhip_marg_hist1d': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     'bfhip_marg_index': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_long, C.c_int]),
@@ -155,7 +159,9 @@ MARG_MAX_BINS, MARG_MAX_BINS2D, MARG_MAX_LD = 1024, 128, 256   # BFHIP_MARG_MAX_
 MARG_EXTENT_WORK = 32768   # BFHIP_MARG_EXTENT_WORK: doubles of bfhip_marg_extent's work buffer
 LOO_TILE, LOO_WS_MAX, LOO_NSUM = 64, 1 << 28, 8   # BFHIP_LOO_TILE / _WS_MAX (doubles) / _NSUM
 LOO_SSE, LOO_PRESS, LOO_MAX, LOO_ARGMAX, LOO_SY, LOO_SYY, LOO_NUNIT = range(7)   # BFHIP_LOO_*: the columns of bfhip_lstsq_loo's sums
-WSTAT_TILE = 2048       # sorted positions per workgroup of bfhip_wstat_cumweights: its work buffer is ceil(n / 2048) doubles
+PLOO_ELL, PLOO_Z, PLOO_NOUT = 0, 1, 16   # BFHIP_PLOO_ELL / _Z / _NOUT
+PLOO_ROWS = ('lpd', 'swe', 'waic', 'elpd_loo', 'khat', 'sigma', 'n_tail', 'cut', 'ess_loo', 'pit', 'max_r', 'flags', 'sw2', 'max_b')   # BFHIP_PLOO_LPD ...
+WSTAT_TILE = 2048      # sorted positions per workgroup of bfhip_wstat_cumweights: its work buffer is ceil(n / 2048) doubles
 
 
 def psis_work_bytes(n):

@@ -353,6 +353,12 @@ class Chi2PipelineDensity(SurrogateDensity):
         from ..utils.predictive import predictive
         return predictive(self, x, **kw)
 
+    def data_loo(self, x, **kw):
+        """Pointwise PSIS-LOO and WAIC of the data points at the ORIGINAL-space draws x, a GPU tensor (n_chain, n_draw, d) or
+        (n, d): ``bayesfast_amd.utils.data_loo(self, x, **kw)``, a ``DataLOO``."""
+        from ..utils.data_loo import data_loo
+        return data_loo(self, x, **kw)
+
     def logp_and_grad(self, x, original_space=True):
         x = np.asarray(x, dtype=np.float64)
         lp, g = self.device().logp_and_grad(x.reshape(-1, self.input_size), original_space)

@@ -506,3 +506,6 @@ extern "C" int bfhip_wstat_quantiles(bfhip_ctx *ctx, long n, const uint64_t *key
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }
+
+// ==== pointwise PSIS-LOO and WAIC of a batch of columns ==============================================================================
+#include "bfhip_ploo.h"

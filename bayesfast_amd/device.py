@@ -9,7 +9,7 @@ import numpy as np
 from . import _lib
 
 __all__ = ['DeviceContext', 'DeviceDensity', 'DevicePolyModel', 'density_desc_from_spec', 'pipeline_desc_from_spec',
-           'polymodel_desc_from_poly', 'get_context']
+           'polymodel_desc_from_poly', 'polymodel_dense_from_poly', 'polymodel_desc_from_dense', 'residual_dense', 'get_context']
 
 _ORDERS = ('linear', 'quadratic', 'cubic-2', 'cubic-3')
 
@@ -475,9 +475,11 @@ class DeviceDensity:
         return logp, energy
 
 
-def polymodel_desc_from_poly(poly):
-    """``PolyModel.poly_spec()`` -> a filled ``bfhip_polymodel_desc`` + the arrays it points to: dense per-output coefficients
-    with the masks scattered, which is what ``_fun_and_jac`` does on every call (modules/poly.py:474-477)."""
+def polymodel_dense_from_poly(poly):
+    """``PolyModel.poly_spec()`` -> the dense per-output arrays of the description, with the masks scattered, which is what
+    ``_fun_and_jac`` does on every call (modules/poly.py:474-477): a dict of d, m, c0 (m,), lin (m, d), quad (m, d, d) or None,
+    mask2 / mask3 (the union of the dimensions the cubic configs touch, per order), cub2 (m, n2, n2), cub3 (m, n3, n3, n3), use_bound
+    and, with a bound, mu, hess, alpha and f_mu (m,)."""
     d, m = int(poly['input_size']), int(poly['output_size'])
     c0 = np.zeros(m)
     lin = np.zeros((m, d))
@@ -517,6 +519,16 @@ def polymodel_desc_from_poly(poly):
             sel = (jj < kk) & (kk < ll)  # only j < k < l is defined (modules/_poly.pyx:86-137)
             for q, o in enumerate(om):
                 cub3[o, pos[jj[sel]], pos[kk[sel]], pos[ll[sel]]] += coef[q][sel]
+    dense = dict(d=d, m=m, c0=c0, lin=lin, quad=quad if has_quad else None, mask2=mask2, cub2=cub2, mask3=mask3, cub3=cub3,
+                 use_bound=bool(poly.get('use_bound', False) and (has_quad or cubic)))  # (not for an all-linear model, modules/poly.py:467)
+    if dense['use_bound']:
+        dense.update(mu=np.asarray(poly['mu'], dtype=np.float64), hess=np.asarray(poly['hess'], dtype=np.float64),
+                     alpha=float(poly['alpha']), f_mu=np.asarray(poly['f_mu'], dtype=np.float64).reshape(m))
+    return dense
+
+
+def polymodel_desc_from_dense(dense):
+    """The arrays of ``polymodel_dense_from_poly`` -> a filled ``bfhip_polymodel_desc`` + the arrays it points to."""
     ds = _lib.PolymodelDesc()
     keep = []
 
@@ -525,22 +537,46 @@ def polymodel_desc_from_poly(poly):
         keep.append(a)
         return a.ctypes.data_as(C.POINTER(C.c_double))
 
-    ds.d, ds.m = d, m
-    ds.c0, ds.lin = f64(c0), f64(lin)
-    if has_quad:
-        ds.quad = f64(quad)
+    mask2, mask3 = (np.ascontiguousarray(dense[k], dtype=np.int32) for k in ('mask2', 'mask3'))
+    ds.d, ds.m = int(dense['d']), int(dense['m'])
+    ds.c0, ds.lin = f64(dense['c0']), f64(dense['lin'])
+    if dense['quad'] is not None:
+        ds.quad = f64(dense['quad'])
     if mask2.size:
         keep.append(mask2)
-        ds.n2, ds.mask2, ds.cubic2 = int(mask2.size), mask2.ctypes.data_as(C.POINTER(C.c_int)), f64(cub2)
+        ds.n2, ds.mask2, ds.cubic2 = int(mask2.size), mask2.ctypes.data_as(C.POINTER(C.c_int)), f64(dense['cub2'])
     if mask3.size:
         keep.append(mask3)
-        ds.n3, ds.mask3, ds.cubic3 = int(mask3.size), mask3.ctypes.data_as(C.POINTER(C.c_int)), f64(cub3)
-    if poly.get('use_bound', False) and (has_quad or cubic):  # (not for an all-linear model, modules/poly.py:467)
+        ds.n3, ds.mask3, ds.cubic3 = int(mask3.size), mask3.ctypes.data_as(C.POINTER(C.c_int)), f64(dense['cub3'])
+    if dense['use_bound']:
         ds.use_bound = 1
-        ds.mu, ds.hess = f64(poly['mu']), f64(poly['hess'])
-        ds.alpha = float(poly['alpha'])
-        ds.f_mu = f64(np.asarray(poly['f_mu'], dtype=np.float64).reshape(m))
+        ds.mu, ds.hess = f64(dense['mu']), f64(dense['hess'])
+        ds.alpha = float(dense['alpha'])
+        ds.f_mu = f64(np.asarray(dense['f_mu'], dtype=np.float64).reshape(ds.m))
     return ds, keep
+
+
+def polymodel_desc_from_poly(poly):
+    """``PolyModel.poly_spec()`` -> a filled ``bfhip_polymodel_desc`` + the arrays it points to."""
+    return polymodel_desc_from_dense(polymodel_dense_from_poly(poly))
+
+
+def residual_dense(dense, y, w):
+    """The model of the whitened residuals z(x) = W (y - f(x)) of the model ``dense`` (``polymodel_dense_from_poly``), y (m,) and
+    W (m, m), in the same dense arrays: every output of a PolyModel is affine in its coefficients -- outside the bound too, where
+    ff = (beta ff_0 - (beta - alpha) f_mu) / alpha has weights that sum to 1 -- so z is a PolyModel on the same inputs, bound and
+    alpha with c0' = W (y - c0), f_mu' = W (y - f_mu) and lin, quad, cub2, cub3 contracted with -W along the output axis."""
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    w = np.asarray(w, dtype=np.float64)
+    m = int(dense['m'])
+    if y.shape != (m,) or w.shape != (m, m):
+        raise ValueError('y should be (%d,) and W (%d, %d).' % (m, m, m))
+    mix = lambda a: None if a is None else (-w @ np.asarray(a, dtype=np.float64).reshape(m, -1)).reshape(np.shape(a))
+    out = dict(dense, c0=w @ (y - dense['c0']), lin=mix(dense['lin']), quad=mix(dense['quad']), cub2=mix(dense['cub2']),
+               cub3=mix(dense['cub3']))
+    if dense['use_bound']:
+        out['f_mu'] = w @ (y - np.asarray(dense['f_mu'], dtype=np.float64).reshape(m))
+    return out
 
 
 class DevicePolyModel:
@@ -550,12 +586,20 @@ class DevicePolyModel:
 
     poly : the dict ``PolyModel.poly_spec()`` returns."""
 
-    def __init__(self, poly, ctx=None):
+    def __init__(self, poly, ctx=None, dense=None):
         self.ctx = ctx if ctx is not None else get_context()
-        self.d, self.m = int(poly['input_size']), int(poly['output_size'])
-        ds, keep = polymodel_desc_from_poly(poly)
+        if dense is None:
+            dense = polymodel_dense_from_poly(poly)
+        self.d, self.m = int(dense['d']), int(dense['m'])
+        ds, keep = polymodel_desc_from_dense(dense)
         self._desc, self._keep = ds, keep
         self._uploaded = None
+
+    @classmethod
+    def from_dense(cls, dense, ctx=None):
+        """A model from the dense arrays of ``polymodel_dense_from_poly`` or ``residual_dense``.  A context holds one uploaded
+        polymodel; whichever model is used next uploads itself again (``upload_if_needed``)."""
+        return cls(None, ctx, dense=dense)
 
     def upload_if_needed(self):
         if self.ctx.__dict__.get('_pm_owner') is not self:

@@ -483,6 +483,13 @@ class TraceTuple:
         from ..utils.predictive import predictive
         return predictive(density, self._diag_input(since_iter, include_warmup, True, 'samples'), log_weights=log_weights, **kw)
 
+    def data_loo(self, density, log_weights=None, since_iter=None, include_warmup=False, **kw):
+        """Pointwise PSIS-LOO and WAIC (``bayesfast_amd.utils.data_loo``: a ``DataLOO``) of the data points of ``density``, a
+        ``Chi2PipelineDensity``, at the original-space draws that ``get(since_iter, include_warmup, flatten=False)`` selects, read
+        where ``sample()`` left them; ``kw`` is ``outputs``.  Device parts only; single process only, as ``predictive``."""
+        from ..utils.data_loo import data_loo
+        return data_loo(density, self._diag_input(since_iter, include_warmup, True, 'samples'), log_weights=log_weights, **kw)
+
     def _local_samples(self, since_iter, include_warmup, original_space):
         """This rank's chains of what ``get(..., flatten=False)`` selects, as a view of the parts (n_chain_local, n_t, n_d),
         unmaterialised; unlike ``_diag_input`` with any number of ranks: for the statistics that are collectives."""

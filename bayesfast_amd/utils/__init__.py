@@ -4,7 +4,9 @@ from .diagnostics import rhat, ess, summary
 from .psis import psis, PSISResult, weighted_summary
 from .marginals import marginals, Marginals
 from .predictive import predictive, Predictive
+from .data_loo import data_loo, pointwise_loo, DataLOO
 from .laplace import Laplace, LaplaceResult, make_positive
 
 __all__ = ['SystematicResampler', 'integrated_time', 'AutocorrError', 'Laplace', 'LaplaceResult', 'make_positive', 'rhat', 'ess', 'summary',
-           'psis', 'PSISResult', 'weighted_summary', 'marginals', 'Marginals', 'predictive', 'Predictive']
+           'psis', 'PSISResult', 'weighted_summary', 'marginals', 'Marginals', 'predictive', 'Predictive', 'data_loo',
+           'pointwise_loo', 'DataLOO']

@@ -37,7 +37,9 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_DIM 128         /* input_size limit of the device path */
 #define BFHIP_MAX_TREEDEPTH 12
 
-/* 110: bfhip_polymodel_columns, a batch of the uploaded polymodel's outputs at draws read in place from the (chain, time, dimension)
+/* 111: bfhip_ploo_moments / _tail / _finish (and bfhip_ploo_work_bytes), pointwise PSIS-LOO and WAIC of a batch of columns of pointwise log
+ * likelihoods with a top-M radix select in place of a sort per column (additions only).
+ * 110: bfhip_polymodel_columns, a batch of the uploaded polymodel's outputs at draws read in place from the (chain, time, dimension)
  * tensor, and the bound radius of every draw (the posterior predictive summaries).
  * 109: bfhip_lstsq_loo, the leave-one-out validation of the least-squares fit (leverages from the kept factor, held-out residuals,
  * per-output sums).
@@ -621,6 +623,54 @@ int bfhip_wstat_moments(bfhip_ctx *ctx, long n, const double *series, const doub
 int bfhip_wstat_cumweights(bfhip_ctx *ctx, long n, const uint32_t *order, const double *w, double *cum, double *work);
 int bfhip_wstat_quantiles(bfhip_ctx *ctx, long n, const uint64_t *keys_sorted, const uint32_t *order, const double *w, const double *cum,
                           const double *wsum, int nq, const double *probs, int b, double *out);
+
+/* Pointwise leave-one-out cross-validation by Pareto-smoothed importance sampling, and WAIC (Vehtari, Gelman, Gabry 2017;
+ * bayesfast_amd/utils/data_loo.py has the definitions), of a batch of nb <= BFHIP_DIAG_BATCH columns of pointwise log likelihoods in a
+ * series buffer: element (row s, column b) at series[s ld + b], ld >= nb, n rows, n <= 2^31 - 1 (BFHIP_ERR_UNSUPPORTED beyond).
+ *   mode  BFHIP_PLOO_ELL: the buffer holds ell_s.  BFHIP_PLOO_Z: it holds z_s and ell_s = c[b] - z_s^2 / 2, c (BFHIP_DIAG_BATCH,) on the device.
+ *   lb    (n,) device base log weights, logsumexp 0, or NULL: -log n each.  A row with lb = -inf is not part of the sample, whatever it
+ *         holds; it counts in n.  The importance ratio that removes the point is r_s = lb_s - ell_s (NULL: -ell_s).
+ *   out   (BFHIP_PLOO_NOUT, BFHIP_DIAG_BATCH) doubles, rows BFHIP_PLOO_LPD ... below; the three stages fill it between them, in this order.
+ *   work  bfhip_ploo_work_bytes(n) bytes of the caller's, 256-byte aligned, the same buffer for the three stages of a batch.
+ * bfhip_ploo_moments: max r, lpd = logsumexp(lb + ell), sum w ell, sum w (ell - sum w ell)^2 on a second pass, sum w^2, max lb and the
+ *   flags 1 (a non-finite ell in a row of non-zero weight) and 4 (no row of non-zero weight).
+ * bfhip_ploo_tail: with M = min(n / 5, ceil(3 sqrt n)), the M + 1 largest ratios r_s - max r of every column in the order of a stable
+ *   ascending sort of the column (among equal keys the lower row first): tail_keys (BFHIP_DIAG_BATCH, M + 1) uint64 order-preserving
+ *   keys, ascending, and tail_idx (BFHIP_DIAG_BATCH, M + 1) uint32 rows; position 0 is the cut of bfhip_psis, sorted position n - M - 1.
+ *   A most-significant-digit radix select over the keys (eight histogram passes with integer counters), a compaction of the rows above
+ *   the cut pair, and two segmented sorts of those M pairs; no column is sorted.  Reads out's BFHIP_PLOO_MAXR row.
+ * bfhip_ploo_finish: per column the generalised-Pareto fit of bfhip_psis on the tail keys (same kernels, same arithmetic), the smoothed
+ *   tail values, and the sums behind elpd_loo = logsumexp(v + ell), ess_loo = 1 / sum exp(2 v) and pit = sum exp(v) Phi(z) (Z mode; NaN
+ *   in ELL mode) for the smoothed, normalised log weights v: rows not above the cut pair with their own ratio in one pass over the
+ *   batch, the M tail rows with their smoothed value, fetched by index.  Flag 2: nothing smoothed (M < 5 or a tail without spread;
+ *   khat = inf).  With flag 1 or 4 every figure of the column but M is NaN.
+ * Every floating-point reduction has an order fixed by n alone and a column never meets its neighbours: bitwise repeatable, whichever
+ * slot or batch a column lands in.  Stream-ordered, no host synchronisation (the sorts keep their temporary storage in the context's
+ * workspace, which synchronises only when it has to grow). */
+#define BFHIP_PLOO_ELL 0
+#define BFHIP_PLOO_Z 1
+#define BFHIP_PLOO_NOUT 16
+#define BFHIP_PLOO_LPD 0      /* logsumexp(lb + ell) */
+#define BFHIP_PLOO_SWE 1      /* sum w ell, w = exp(lb) */
+#define BFHIP_PLOO_WAIC 2     /* sum w (ell - sum w ell)^2 */
+#define BFHIP_PLOO_ELPD 3     /* elpd_loo */
+#define BFHIP_PLOO_KHAT 4
+#define BFHIP_PLOO_SIGMA 5
+#define BFHIP_PLOO_M 6
+#define BFHIP_PLOO_CUT 7      /* the cut, r - max r at sorted position n - M - 1 */
+#define BFHIP_PLOO_ESS 8      /* 1 / sum exp(2 v) */
+#define BFHIP_PLOO_PIT 9
+#define BFHIP_PLOO_MAXR 10    /* max r */
+#define BFHIP_PLOO_FLAGS 11
+#define BFHIP_PLOO_SW2 12     /* sum w^2 */
+#define BFHIP_PLOO_MAXB 13    /* max lb; rows 14 and 15 are the stages' own */
+size_t bfhip_ploo_work_bytes(long n);
+int bfhip_ploo_moments(bfhip_ctx *ctx, long n, const double *series, long ld, int nb, int mode, const double *c, const double *lb,
+                       double *out, void *work, size_t work_bytes);
+int bfhip_ploo_tail(bfhip_ctx *ctx, long n, const double *series, long ld, int nb, int mode, const double *c, const double *lb,
+                    const double *out, uint64_t *tail_keys, uint32_t *tail_idx, void *work, size_t work_bytes);
+int bfhip_ploo_finish(bfhip_ctx *ctx, long n, const double *series, long ld, int nb, int mode, const double *c, const double *lb,
+                      const uint64_t *tail_keys, const uint32_t *tail_idx, double *out, void *work, size_t work_bytes);
 
 /* Marginal posterior histograms and credible levels of (weighted) draws (bayesfast_amd/utils/marginals.py has the definitions), on a
  * batch of at most BFHIP_DIAG_BATCH parameters in a (n, BFHIP_DIAG_BATCH) series buffer as bfhip_wstat_columns writes it with w = NULL.
