@@ -146,10 +146,14 @@ SYMBOLS = {
     'bfhip_laplace_opt': (C.c_int, [_vp, C.POINTER(LaplaceOpts), C.c_int, _vp, _vp, _vp, _vp, _vp]),
     'bfhip_pipeline_logp_hess': (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     'bfhip_pipeline_laplace_opt': (C.c_int, [_vp, C.POINTER(LaplaceOpts), C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    'bfhip_profile_lines': (C.c_int, [_vp, C.POINTER(LaplaceOpts), C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'bfhip_pipeline_profile_lines': (C.c_int, [_vp, C.POINTER(LaplaceOpts), C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _vp]),
     'bfhip_wave_sum_probe': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     'bfhip_wave_packs_probe': (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
 }
 HESS_FULL, HESS_GAUSS_NEWTON = 0, 1   # BFHIP_HESS_FULL / _GAUSS_NEWTON: hess_kind of the bfhip_pipeline_* Hessian calls
+PROFILE_SAMPLING, PROFILE_ORIGINAL, PROFILE_NOT_RUN = 0, 1, 4   # BFHIP_PROFILE_*: the objective of the profile calls; the status of a grid value that was not run
 WSUM_MAX = 7            # BFHIP_WSUM_MAX: values bfhip_wave_sum_probe reduces together
 WSUM_FORMS = {'built': 0, 'packed': 1, 'unpacked': 2}   # BFHIP_WSUM_BUILT / _PACKED / _UNPACKED
 ACOR_MAX_GROUPS = 256   # walker groups of bfhip_acor_lag_sums: its work buffer is min(n_w, 256) * n_lag * n_d doubles

@@ -256,6 +256,13 @@ class SurrogateDensity:
         return self.device().logp_grad_hess(x, original_space)[2].cpu().numpy()
 
 
+    def profile(self, **kw):
+        """Profiles of this density along parameters and pairs of parameters, on the device: ``bayesfast_amd.utils.profile(self,
+        **kw)``, a ``Profile``."""
+        from ..utils.profile import profile
+        return profile(self, **kw)
+
+
 class Chi2PipelineDensity(SurrogateDensity):
     """A pipeline evaluated AND sampled on the device: a multi-output ``PolyModel`` surrogate (x -> m outputs), a Gaussian
     likelihood of those outputs and, optionally, a diagonal Gaussian prior of the inputs, i.e. the reference's

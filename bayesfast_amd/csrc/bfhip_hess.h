@@ -396,23 +396,50 @@ struct BfNewtonStat {
 //   void Ev::store(BfNewtonWork &nw, int tid, int nt)   H of the LAST eval -> upper triangle of nw.M and nw.hd, its gradient -> nw.gc,
 //                                                       then a barrier
 // On return the last eval was taken at the returned point nw.x and stored.
+//
+// fixed (d bytes, any address space; NULL: none) holds coordinates in place: the step of a fixed coordinate is exactly zero and its
+// x leaves with the bits it came in with.  After every store, row and column i of the stored matrix become an identity row (hd_i = -1:
+// the pivot of -H + lambda I is lambda + 1) and gc_i = 0, so the factor's entries in that row are exactly zero and all indexing stays
+// as it is.  The convergence measure, the damping scale and hence the Levenberg shift range over the free coordinates only.  With
+// no free coordinate the call evaluates once: status 0 (2 for a non-finite value), 0 iterations.
+__host__ __device__ inline void bf_newton_mask(BfNewtonWork &nw, int d, const uint8_t *fixed, int tid, int nt) {
+    for (int idx = tid; idx < bf_tri_slots(d); idx += nt) {
+        int i, j;
+        if (!bf_tri_pair(d, idx, i, j)) continue;   // (i >= j)
+        if (!fixed[i] && !fixed[j]) continue;
+        if (i == j) {
+            nw.hd[i] = -1.;
+            nw.gc[i] = 0.;
+        } else {
+            nw.M[(size_t)j * nw.ld + i] = 0.;
+        }
+    }
+    BF_HESS_SYNC();
+}
+
 template <class Ev>
 __host__ __device__ inline BfNewtonStat bf_newton_run(Ev &ev, int d, const double *x0, int max_iter, double xtol, BfNewtonWork &nw, int tid,
-                                                      int nt) {
+                                                      int nt, const uint8_t *fixed = NULL) {
     BfNewtonStat res;
     res.n_iter = 0;
     res.status = 1;
     res.last_step = 0.;
     res.lam = 0.;
+    int n_free = d;
+    if (fixed)
+        for (int i = 0; i < d; ++i) n_free -= fixed[i] ? 1 : 0;
     BF_HESS_SYNC();
     for (int i = tid; i < d; i += nt) nw.x[i] = x0[i];
     BF_HESS_SYNC();
     double f = ev.eval(nw.x, tid, nt), lam_prev = 0.;
     ev.store(nw, tid, nt);
+    if (fixed) bf_newton_mask(nw, d, fixed, tid, nt);
     if (!bf_finite(f)) res.status = 2;
+    else if (n_free == 0) res.status = 0;
     for (int it = 0; it < max_iter && res.status == 1; ++it) {
         double hmax = 0.;
-        for (int i = 0; i < d; ++i) hmax = fmax(hmax, fabs(nw.hd[i]));
+        for (int i = 0; i < d; ++i)
+            if (!fixed || !fixed[i]) hmax = fmax(hmax, fabs(nw.hd[i]));
         const double lam0 = hmax > 0. ? 1e-3 * hmax : 1e-3;
         double lam = 0., ms = 0., ft = f;
         int accepted = 0;
@@ -420,8 +447,9 @@ __host__ __device__ inline BfNewtonStat bf_newton_run(Ev &ev, int d, const doubl
             if (bf_newton_chol(nw, d, lam, tid, nt)) {
                 bf_newton_solve(nw, d, tid, nt);
                 ms = 0.;
-                for (int i = 0; i < d; ++i) ms += fabs(nw.r[i]);
-                ms /= (double)d;
+                for (int i = 0; i < d; ++i)
+                    if (!fixed || !fixed[i]) ms += fabs(nw.r[i]);
+                ms /= (double)n_free;
                 if (!bf_finite(ms)) {
                     res.status = 2;
                     break;
@@ -432,7 +460,7 @@ __host__ __device__ inline BfNewtonStat bf_newton_run(Ev &ev, int d, const doubl
                     res.lam = lam;
                     break;
                 }
-                for (int i = tid; i < d; i += nt) nw.xt[i] = nw.x[i] + nw.r[i];
+                for (int i = tid; i < d; i += nt) nw.xt[i] = (fixed && fixed[i]) ? nw.x[i] : nw.x[i] + nw.r[i];
                 BF_HESS_SYNC();
                 ft = ev.eval(nw.xt, tid, nt);
                 // (near the maximum the increase falls below the rounding of logp itself)
@@ -450,11 +478,13 @@ __host__ __device__ inline BfNewtonStat bf_newton_run(Ev &ev, int d, const doubl
             // the work vectors may hold a rejected trial point: evaluate the point that is returned
             (void)ev.eval(nw.x, tid, nt);   // (f is logp at nw.x already)
             ev.store(nw, tid, nt);
+            if (fixed) bf_newton_mask(nw, d, fixed, tid, nt);
             break;
         }
         for (int i = tid; i < d; i += nt) nw.x[i] = nw.xt[i];
         f = ft;
         ev.store(nw, tid, nt);   // (its barrier also publishes x)
+        if (fixed) bf_newton_mask(nw, d, fixed, tid, nt);
         res.n_iter = it + 1;
         res.last_step = ms;
         res.lam = lam;
@@ -464,6 +494,60 @@ __host__ __device__ inline BfNewtonStat bf_newton_run(Ev &ev, int d, const doubl
     res.logp = f;
     return res;
 }
+
+// ---- the objective of a profile: an evaluation Ev (one with the members w and pt: BfScalarNewtonEval, PldNewtonEval) seen as ------
+//   BFHIP_PROFILE_SAMPLING (0)   Ev itself, the function the maximiser climbs
+//   BFHIP_PROFILE_ORIGINAL (1)   logp_orig(T(x)): Ev minus sum_i log|T'_i(x_i)|, its gradient minus d log|T'_i| / dx_i, its Hessian's
+//                                diagonal minus d2 log|T'_i| / dx_i^2 -- the three vectors lj, gj, lj2 the evaluation leaves behind.
+// The sum is taken by every thread in index order.  Without a transform the two are the same function and the same instructions.
+// Where the decay term is on, the original objective also takes that term's true derivatives (store, below).
+template <class Ev>
+struct BfProfileEval {
+    Ev &ev;
+    int objective;
+    __host__ __device__ bool shifted() const { return objective == 1 && ev.pt.tr; }
+    __host__ __device__ double eval(const double *x, int tid, int nt) {
+        double f = ev.eval(x, tid, nt);
+        if (shifted()) {
+            double logdet = 0.;
+            for (int i = 0; i < ev.m.d; ++i) logdet += ev.w.lj[i];
+            f -= logdet;
+        }
+        return f;
+    }
+    __host__ __device__ void store(BfNewtonWork &nw, int tid, int nt) {
+        ev.store(nw, tid, nt);
+        if (!shifted()) return;
+        const int d = ev.m.d, DP = ev.m.DP;
+        const double gam = ev.m.decay_gamma;
+        if (ev.pt.dec) {
+            // The sampling-space gradient carries the decay term WITHOUT the transform's Jacobian (bfhip_hess.h, top), so it is not
+            // the derivative of the value, and its zero is not the value's maximum.  A profile is a statement about the value: here
+            // the decay term -gamma (xo - mu_d)^T H_d (xo - mu_d) is chained through T like every other term,
+            //   gradient  -2 gamma dg_i J_i,   Hessian  -gamma (H_d[j][i] + H_d[i][j]) J_i J_j - delta_ij 2 gamma dg_i T''_i    (T'' = gj J)
+            // in place of -2 gamma dg_i and -gamma (H_d[j][i] J_j + H_d[i][j] J_i).
+            // dg = H_d^T (xo - mu_d) is the term's gradient only for a symmetric H_d, which it is (the inverse covariance of the fit
+            // points); the Hessian is written with H_d + H_d^T so that it stays symmetric bit for bit.
+            for (int idx = tid; idx < bf_tri_slots(d); idx += nt) {
+                int i, j;
+                if (!bf_tri_pair(d, idx, i, j)) continue;   // (i >= j)
+                const double hji = bf_frag_at(ev.m.Hdf, DP, j, i), hij = bf_frag_at(ev.m.Hdf, DP, i, j);
+                const double Ji = ev.w.J[i], Jj = ev.w.J[j];
+                const double c = -gam * (((hji + hij) * (Ji * Jj) - hji * Ji) - hij * Jj);
+                if (i == j) nw.hd[i] += c - 2. * gam * (ev.w.dg[i] * (ev.w.gj[i] * Ji));
+                else nw.M[(size_t)j * nw.ld + i] += c;
+            }
+        }
+        for (int i = tid; i < d; i += nt) {
+            double g = nw.gc[i] - ev.w.gj[i];
+            if (ev.pt.dec) g -= 2. * gam * (ev.w.dg[i] * (ev.w.J[i] - 1.));
+            nw.gc[i] = g;
+        }
+        BF_HESS_SYNC();
+        for (int i = tid; i < d; i += nt) nw.hd[i] -= ev.w.lj2[i];   // (behind the barrier: hd_i may have been another thread's above)
+        BF_HESS_SYNC();
+    }
+};
 
 // ---- the scalar surrogate density as that evaluation ----
 struct BfScalarNewtonEval {

@@ -393,4 +393,9 @@ struct PldNewtonEval {
         __syncthreads();
     }
 };
+
+// host side (bfhip_pld_hess.hip): the refusals, the LDS need (pldh_lds_doubles + lds_extra_doubles), the grid and the work buffer of
+// a launch of n points on this evaluation
+struct bfhip_ctx;
+int plh_prepare(bfhip_ctx *ctx, const char *who, int hess_kind, int n, size_t lds_extra_doubles, size_t *lds_bytes, int *grid);
 #endif  // BF_HOST_EMU

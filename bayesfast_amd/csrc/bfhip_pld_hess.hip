@@ -69,8 +69,8 @@ __global__ __launch_bounds__(PLDH_TH) void bf_pld_laplace_opt_kernel(DevModel m,
     }
 }
 
-// the checks both calls share, the grid and the work buffer: *grid workgroups, each with its slot
-static int plh_prepare(bfhip_ctx *ctx, const char *who, int hess_kind, int n, size_t lds_extra_doubles, size_t *lds_bytes, int *grid) {
+// the checks every call on the evaluation shares (bfhip_profile.hip too), the grid and the work buffer: *grid workgroups, each with its slot
+int plh_prepare(bfhip_ctx *ctx, const char *who, int hess_kind, int n, size_t lds_extra_doubles, size_t *lds_bytes, int *grid) {
     if (!ctx->has_model) return bf_set_error(BFHIP_ERR_STATE, "%s: no density uploaded", who);
     const DevModel &m = ctx->model;
     if (!m.pld.on)

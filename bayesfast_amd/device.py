@@ -385,7 +385,7 @@ class DeviceDensity:
                                                  _ptr(hess)))
         return (logp[0], grad[0], hess[0]) if single else (logp, grad, hess)
 
-    MAXIMIZE_STATUS = ('converged', 'max_iter reached', 'non-finite logp', 'the last step was short but damped')
+    MAXIMIZE_STATUS = ('converged', 'max_iter reached', 'non-finite logp', 'the last step was short but damped', 'not run')
 
     def maximize(self, x0, max_iter=200, xtol=1e-5):
         """Damped Newton maximisation of logp in the sampling space from every row of x0 (n_start, d) or (d,), all starts in one
@@ -439,6 +439,52 @@ class DeviceDensity:
         kind = _lib.HESS_GAUSS_NEWTON if gauss_newton else _lib.HESS_FULL
         _lib.check(self.ctx._lib.bfhip_pipeline_laplace_opt(self.ctx.handle, C.byref(opts), kind, n, _ptr(xt), _ptr(out['x']),
                                                             _ptr(out['logp']), _ptr(out['hess']), _ptr(out['info'])))
+        return out
+
+    PROFILE_OBJECTIVES = {'sampling': _lib.PROFILE_SAMPLING, 'original': _lib.PROFILE_ORIGINAL}
+
+    def _profile_args(self, fixed, walk, x_start, values, objective):
+        """The arguments of the two profile calls as device tensors of the ABI's types, and the empty result dict."""
+        torch = _torch()
+        self.upload_if_needed()
+        if objective not in self.PROFILE_OBJECTIVES:
+            raise ValueError("objective should be 'sampling' or 'original'.")
+        xs = self.ctx.tensor(x_start, torch.float64).reshape(-1, self.d)
+        n = xs.shape[0]
+        fx = self.ctx.tensor(np.asarray(fixed, dtype=np.uint8) if not isinstance(fixed, torch.Tensor) else fixed, torch.uint8)
+        fx = fx.expand(n, self.d).contiguous() if fx.dim() == 1 else fx.reshape(n, self.d)
+        wk = self.ctx.tensor(np.asarray(walk, dtype=np.int32) if not isinstance(walk, torch.Tensor) else walk, torch.int32)
+        wk = wk.reshape(1).expand(n).contiguous() if wk.numel() == 1 else wk.reshape(n)
+        vals = None if values is None else self.ctx.tensor(values, torch.float64).reshape(n, -1)
+        n_val = 1 if vals is None else vals.shape[1]
+        out = dict(x=self.ctx.empty((n, n_val, self.d)), logp=self.ctx.empty((n, n_val)), info=self.ctx.empty((n, n_val, 4)))
+        return n, n_val, fx, wk, xs, vals, out, self.PROFILE_OBJECTIVES[objective]
+
+    def profile_lines(self, fixed, walk, x_start, values=None, objective='original', max_iter=50, xtol=1e-6):
+        """Grid lines of a profile of this (scalar) density, all in one launch (``bfhip_profile_lines``, a workgroup per line),
+        everything in the SAMPLING coordinates.  Line l holds the coordinates with ``fixed[l, i] != 0`` at their ``x_start[l]`` values
+        except ``walk[l]``, which must be one of them and takes ``values[l, k]`` in turn; every value is one masked Newton
+        maximisation over the free coordinates, started at the optimum of the value before it.  ``fixed`` (n_line, d) or (d,),
+        ``walk`` (n_line,) or one int, ``x_start`` (n_line, d), ``values`` (n_line, n_val).  ``walk = -1`` moves nothing (one masked
+        maximisation from ``x_start``; ``values`` is then None or one column).  ``objective``: ``'original'``, the original-space
+        density parametrised by the sampling coordinates (what a profile is taken of), or ``'sampling'``, the function ``maximize``
+        climbs.  A NaN in ``values`` ends its line.  Returns a dict of float64 device tensors: ``x`` (n_line, n_val, d), ``logp``
+        (n_line, n_val), ``info`` (n_line, n_val, 4) as ``maximize``, with status 4 (``'not run'``) behind a NaN.  ValueError for a
+        walk coordinate outside its line's mask.  The call synchronises the stream (it reads the mask back to check it)."""
+        n, n_val, fx, wk, xs, vals, out, obj = self._profile_args(fixed, walk, x_start, values, objective)
+        opts = _lib.LaplaceOpts(int(max_iter), float(xtol))
+        _lib.check(self.ctx._lib.bfhip_profile_lines(self.ctx.handle, C.byref(opts), obj, n, n_val, _ptr(fx), _ptr(wk), _ptr(xs), _ptr(vals),
+                                                     _ptr(out['x']), _ptr(out['logp']), _ptr(out['info'])))
+        return out
+
+    def pipeline_profile_lines(self, fixed, walk, x_start, values=None, objective='original', max_iter=50, xtol=1e-6, gauss_newton=False):
+        """``profile_lines`` for a pipeline density (``bfhip_pipeline_profile_lines``): the same lines, the same dict of results;
+        ``gauss_newton`` selects the matrix the iteration steps on.  NotImplementedError as ``pipeline_maximize``."""
+        n, n_val, fx, wk, xs, vals, out, obj = self._profile_args(fixed, walk, x_start, values, objective)
+        opts = _lib.LaplaceOpts(int(max_iter), float(xtol))
+        kind = _lib.HESS_GAUSS_NEWTON if gauss_newton else _lib.HESS_FULL
+        _lib.check(self.ctx._lib.bfhip_pipeline_profile_lines(self.ctx.handle, C.byref(opts), kind, obj, n, n_val, _ptr(fx), _ptr(wk),
+                                                              _ptr(xs), _ptr(vals), _ptr(out['x']), _ptr(out['logp']), _ptr(out['info'])))
         return out
 
     _WHICH = {'from_original': 0, 'from_original_grad': 1, 'from_original_grad2': 2, 'to_original': 3,

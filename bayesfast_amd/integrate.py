@@ -292,6 +292,9 @@ def reference_classes(bayesfast=None):
         def data_loo(self, *args, **kwargs):
             return self._inner.data_loo(*args, **kwargs)
 
+        def profile(self, *args, **kwargs):
+            return self._inner.profile(*args, **kwargs)
+
         # ---- per-chain traces of the reference's own classes, for _get_step_size / _get_metric / users ----
         @property
         def _sample_traces(self):

@@ -490,6 +490,14 @@ class TraceTuple:
         from ..utils.data_loo import data_loo
         return data_loo(density, self._diag_input(since_iter, include_warmup, True, 'samples'), log_weights=log_weights, **kw)
 
+    def profile(self, density, since_iter=None, include_warmup=False, **kw):
+        """Profiles (``bayesfast_amd.utils.profile``: a ``Profile``) of ``density``, a ``SurrogateDensity`` or ``Chi2PipelineDensity``:
+        the maximisation starts at the posterior mean of the sampling-space draws that ``get(since_iter, include_warmup,
+        original_space=False, flatten=False)`` selects, and their standard deviation is the default grid scale; ``kw`` are the other
+        arguments of ``profile``.  Single process only, as ``summary``."""
+        from ..utils.profile import profile_from_draws
+        return profile_from_draws(self._diag_input(since_iter, include_warmup, False, 'samples'), density, **kw)
+
     def _local_samples(self, since_iter, include_warmup, original_space):
         """This rank's chains of what ``get(..., flatten=False)`` selects, as a view of the parts (n_chain_local, n_t, n_d),
         unmaterialised; unlike ``_diag_input`` with any number of ranks: for the statistics that are collectives."""

@@ -6,7 +6,8 @@ from .marginals import marginals, Marginals
 from .predictive import predictive, Predictive
 from .data_loo import data_loo, pointwise_loo, DataLOO
 from .laplace import Laplace, LaplaceResult, make_positive
+from .profile import profile, Profile, ProfileInterval
 
 __all__ = ['SystematicResampler', 'integrated_time', 'AutocorrError', 'Laplace', 'LaplaceResult', 'make_positive', 'rhat', 'ess', 'summary',
            'psis', 'PSISResult', 'weighted_summary', 'marginals', 'Marginals', 'predictive', 'Predictive', 'data_loo',
-           'pointwise_loo', 'DataLOO']
+           'pointwise_loo', 'DataLOO', 'profile', 'Profile', 'ProfileInterval']

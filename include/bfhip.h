@@ -37,7 +37,9 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_DIM 128         /* input_size limit of the device path */
 #define BFHIP_MAX_TREEDEPTH 12
 
-/* 111: bfhip_ploo_moments / _tail / _finish (and bfhip_ploo_work_bytes), pointwise PSIS-LOO and WAIC of a batch of columns of pointwise log
+/* 112: bfhip_profile_lines and bfhip_pipeline_profile_lines, profiles of the density along grid lines: the device Newton maximiser
+ * with coordinates held fixed, walked outward in continuation (additions only).
+ * 111: bfhip_ploo_moments / _tail / _finish (and bfhip_ploo_work_bytes), pointwise PSIS-LOO and WAIC of a batch of columns of pointwise log
  * likelihoods with a top-M radix select in place of a sort per column (additions only).
  * 110: bfhip_polymodel_columns, a batch of the uploaded polymodel's outputs at draws read in place from the (chain, time, dimension)
  * tensor, and the bound radius of every draw (the posterior predictive summaries).
@@ -769,6 +771,38 @@ int bfhip_pipeline_logp_hess(bfhip_ctx *ctx, int n, const double *x, int origina
                              double *hess);
 int bfhip_pipeline_laplace_opt(bfhip_ctx *ctx, const bfhip_laplace_opts *opts, int hess_kind, int n_start, const double *x0, double *x,
                                double *logp, double *hess, double *info);
+
+/* Profiles of the uploaded density: at every value of one coordinate, the maximum over the coordinates that are not held fixed.
+ * n_line independent grid lines, one workgroup each (the pipeline form: a capped grid whose workgroups walk over the lines), every
+ * array in the SAMPLING coordinates.  Line l holds the coordinates with fixed[l][i] != 0 at their x_start[l] values, except
+ * walk[l], which must be one of them: for k = 0 .. n_val - 1 it sets x[walk[l]] = values[l][k], maximises the objective over the
+ * free coordinates with the iteration of bfhip_laplace_opt -- from the optimum of value k - 1, from x_start[l] for k = 0; no tangent
+ * predictor -- and writes the point x[l][k], the objective's value logp[l][k] and info[l][k] (the four numbers of bfhip_laplace_opt).
+ * A fixed coordinate's step is exactly zero: it is returned with the bits it was given.  The convergence measure, the damping
+ * scale and the Levenberg shift range over the free coordinates; a line with none evaluates once per value (status 0, 0 iterations).
+ *   objective BFHIP_PROFILE_SAMPLING   the function bfhip_laplace_opt climbs (the sampling-space density)
+ *             BFHIP_PROFILE_ORIGINAL   the original-space density parametrised by the sampling coordinates, logp_orig(T(x)): the
+ *                                      sampling-space one without the transform's log-Jacobian, and where the decay term is on
+ *                                      with that term's true derivatives (the sampling-space gradient carries it without the
+ *                                      transform's Jacobian).  What a profile is taken of; hard bounds stay respected.  Without a
+ *                                      transform both are the same function, bit for bit.
+ *   a NaN in values ends its line: that column and the later ones hold NaN and status 4 (not run)
+ *   a maximisation that ends with status 2 is written as such; the next value starts from the last optimum whose status was not 2
+ *   walk[l] = -1 moves nothing: one masked maximisation from x_start[l].  It takes n_val == 1 (values may then be NULL).  With an
+ *   all-zero mask and BFHIP_PROFILE_SAMPLING it returns what bfhip_laplace_opt / bfhip_pipeline_laplace_opt return, bit for bit.
+ * BFHIP_ERR_ARG: an unknown objective; n_val < 1; a walk coordinate out of range or outside its line's mask; walk = -1 with n_val != 1.
+ * BFHIP_ERR_UNSUPPORTED: the scalar call on a pipeline density and the reverse; the pipeline call where bfhip_pipeline_laplace_opt
+ * refuses (the streamed form, an LDS or work-buffer need above the limit); it uses the same work buffer, grown the same way.
+ * A line's result depends on its own rows and the density only -- not on n_line, nor on the workgroup that ran it.
+ * Both calls read fixed and walk back to check them: they SYNCHRONISE the stream before they launch. */
+#define BFHIP_PROFILE_SAMPLING 0
+#define BFHIP_PROFILE_ORIGINAL 1
+#define BFHIP_PROFILE_NOT_RUN 4
+int bfhip_profile_lines(bfhip_ctx *ctx, const bfhip_laplace_opts *opts, int objective, int n_line, int n_val, const uint8_t *fixed,
+                        const int32_t *walk, const double *x_start, const double *values, double *x, double *logp, double *info);
+int bfhip_pipeline_profile_lines(bfhip_ctx *ctx, const bfhip_laplace_opts *opts, int hess_kind, int objective, int n_line, int n_val,
+                                 const uint8_t *fixed, const int32_t *walk, const double *x_start, const double *values, double *x,
+                                 double *logp, double *info);
 
 /* The sampler kernels' sum over the 64 lanes of a wave (csrc/bfhip_wave.h: v_mfma_f64_4x4x4 steps on the matrix pipe and two row
  * rotations), on given lane values: in (n_batch, n_val, 64) -> out (n_batch, n_val), n_val values reduced together as the kernels
