@@ -10,11 +10,11 @@ from .core.module import Surrogate
 from .core.density import SurrogateDensity, Chi2PipelineDensity, GaussianLink
 from .core.sample import sample
 from .samplers import NTrace, HTrace, TNTrace, GaussianBase, TraceTuple
-from .utils import SystematicResampler, data_loo, pointwise_loo, DataLOO
+from .utils import SystematicResampler, data_loo, pointwise_loo, DataLOO, reweight_moments, data_reweight, Reweighted
 from .core.refit import select_fit_points, importance_weights
 from .transforms import SIT
 from .evidence import GBS, GIS, GHM, bridge, importance, harmonic
 
 __all__ = ['PolyConfig', 'PolyModel', 'FitReport', 'Surrogate', 'SurrogateDensity', 'Chi2PipelineDensity', 'GaussianLink', 'sample', 'NTrace', 'HTrace', 'TNTrace', 'GaussianBase', 'TraceTuple',
            'SystematicResampler', 'select_fit_points', 'importance_weights', 'SIT', 'GBS', 'GIS', 'GHM', 'bridge', 'importance',
-           'harmonic', 'data_loo', 'pointwise_loo', 'DataLOO']
+           'harmonic', 'data_loo', 'pointwise_loo', 'DataLOO', 'reweight_moments', 'data_reweight', 'Reweighted']

@@ -366,6 +366,18 @@ class Chi2PipelineDensity(SurrogateDensity):
         from ..utils.data_loo import data_loo
         return data_loo(self, x, **kw)
 
+    def data_reweight(self, x, y_new, **kw):
+        """The posterior reweighted to the alternative data vectors y_new (K, m) or (m,) at the ORIGINAL-space draws x, a GPU tensor
+        (n_chain, n_draw, d) or (n, d): ``bayesfast_amd.utils.data_reweight(self, x, y_new, **kw)``, a ``Reweighted``."""
+        from ..utils.reweight import data_reweight
+        return data_reweight(self, x, y_new, **kw)
+
+    def data_log_ratio(self, x, y_new, **kw):
+        """The (n_chain, n_draw, K) device tensor of l_k(x) = log L(x | y_k) - log L(x | y) at the ORIGINAL-space draws x:
+        ``bayesfast_amd.utils.reweight.data_log_ratio(self, x, y_new, **kw)``."""
+        from ..utils.reweight import data_log_ratio
+        return data_log_ratio(self, x, y_new, **kw)
+
     def logp_and_grad(self, x, original_space=True):
         x = np.asarray(x, dtype=np.float64)
         lp, g = self.device().logp_and_grad(x.reshape(-1, self.input_size), original_space)

@@ -540,18 +540,8 @@ __global__ __launch_bounds__(PS_T) void pl_finish_kernel(PlCols a, long M, int n
     if (bad) out[PL_LPD * PL_B + b] = out[PL_SWE * PL_B + b] = out[PL_WAIC * PL_B + b] = out[PL_MAXR * PL_B + b] = nan;
 }
 
-extern "C" int bfhip_ploo_finish(bfhip_ctx *ctx, long n, const double *series, long ld, int nb, int mode, const double *c, const double *lb,
-                                 const uint64_t *tail_keys, const uint32_t *tail_idx, double *out, void *work, size_t work_bytes) {
-    BfDeviceGuard dev_guard(ctx);
-    if (int rc = pl_check("bfhip_ploo_finish", ctx, n, series, ld, nb, mode, c)) return rc;
-    if (!out || !tail_keys || !tail_idx || !work || work_bytes < bfhip_ploo_work_bytes(n))
-        return bf_set_error(BFHIP_ERR_ARG, "bfhip_ploo_finish: invalid argument");
-    const long M = pl_tail_size(n);
-    const int m = 30 + (int)floor(sqrt((double)M));
-    if (m > PS_MAXM) return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_ploo_finish: %d candidate thetas", m);
-    const PlWork w = pl_work(work, n);
-    const PlCols a = {n, series, ld, nb, mode, c, lb};
-    hipStream_t st = ctx->stream;
+// the fit per column (w.out8) and the smoothed tail values (w.sm): bfhip_ploo_finish and bfhip_rw_finish (bfhip_rw.h) launch the same
+static void pl_fit_and_smooth(hipStream_t st, const PlWork &w, int nb, long M, int m, const uint64_t *tail_keys) {
     hipLaunchKernelGGL(pl_fit_init_kernel, dim3(1), dim3(PL_B * 8), 0, st, w.out8);
     for (int b = 0; b < nb; ++b) {   // the fit of bfhip_psis on an ascending key array of length M + 1: its n is M + 1
         const uint64_t *ks = tail_keys + (long)b * (M + 1);
@@ -566,6 +556,21 @@ extern "C" int bfhip_ploo_finish(bfhip_ctx *ctx, long n, const double *series, l
     if (M > 0)
         hipLaunchKernelGGL(pl_smooth_kernel, dim3((unsigned)((M + PS_T - 1) / PS_T), nb), dim3(PS_T), 0, st, M, tail_keys,
                            (const double *)w.out8, w.sm);
+}
+
+extern "C" int bfhip_ploo_finish(bfhip_ctx *ctx, long n, const double *series, long ld, int nb, int mode, const double *c, const double *lb,
+                                 const uint64_t *tail_keys, const uint32_t *tail_idx, double *out, void *work, size_t work_bytes) {
+    BfDeviceGuard dev_guard(ctx);
+    if (int rc = pl_check("bfhip_ploo_finish", ctx, n, series, ld, nb, mode, c)) return rc;
+    if (!out || !tail_keys || !tail_idx || !work || work_bytes < bfhip_ploo_work_bytes(n))
+        return bf_set_error(BFHIP_ERR_ARG, "bfhip_ploo_finish: invalid argument");
+    const long M = pl_tail_size(n);
+    const int m = 30 + (int)floor(sqrt((double)M));
+    if (m > PS_MAXM) return bf_set_error(BFHIP_ERR_UNSUPPORTED, "bfhip_ploo_finish: %d candidate thetas", m);
+    const PlWork w = pl_work(work, n);
+    const PlCols a = {n, series, ld, nb, mode, c, lb};
+    hipStream_t st = ctx->stream;
+    pl_fit_and_smooth(st, w, nb, M, m, tail_keys);
     const int g = ps_grid(n, BF_SLICES);
     hipLaunchKernelGGL(pl_body_kernel, dim3(g), dim3(PS_T), 0, st, a, M, (const double *)out, tail_keys, tail_idx, w.part);
     hipLaunchKernelGGL(pl_finish_kernel, dim3(nb), dim3(PS_T), 0, st, a, M, g, (const double *)w.part, tail_idx, (const double *)w.sm,

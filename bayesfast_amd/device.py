@@ -625,6 +625,25 @@ def residual_dense(dense, y, w):
     return out
 
 
+def linear_dense(dense, a, b):
+    """The K-output model g(x) = A f(x) + b of the model ``dense`` (``polymodel_dense_from_poly``), A (K, m) and b (K,), in the same
+    dense arrays: every output of a PolyModel is affine in its coefficients, outside the bound too (``residual_dense`` has the
+    argument), so g is a PolyModel on the same inputs, bound and alpha with c0' = A c0 + b, f_mu' = A f_mu + b and lin, quad, cub2,
+    cub3 contracted with A along the output axis; mu, hess, alpha and the masks are unchanged."""
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    m = int(dense['m'])
+    if a.ndim != 2 or a.shape[1] != m or b.shape != (a.shape[0],) or a.shape[0] < 1:
+        raise ValueError('A should be (K, %d) and b (K,).' % m)
+    k = a.shape[0]
+    mix = lambda v: None if v is None else (a @ np.asarray(v, dtype=np.float64).reshape(m, -1)).reshape((k,) + np.shape(v)[1:])
+    out = dict(dense, m=k, c0=a @ np.asarray(dense['c0'], dtype=np.float64).reshape(m) + b, lin=mix(dense['lin']), quad=mix(dense['quad']),
+               cub2=mix(dense['cub2']), cub3=mix(dense['cub3']))
+    if dense['use_bound']:
+        out['f_mu'] = a @ np.asarray(dense['f_mu'], dtype=np.float64).reshape(m) + b
+    return out
+
+
 class DevicePolyModel:
     """A multi-output PolyModel resident on one GPU: ``PolyModel.fun / jac / fun_and_jac`` over batches of points
     (modules/poly.py:430-503) for linear, quadratic and cubic configs; masks are scattered to dense per-output

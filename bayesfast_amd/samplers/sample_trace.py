@@ -490,6 +490,14 @@ class TraceTuple:
         from ..utils.data_loo import data_loo
         return data_loo(density, self._diag_input(since_iter, include_warmup, True, 'samples'), log_weights=log_weights, **kw)
 
+    def data_reweight(self, density, y_new, log_weights=None, since_iter=None, include_warmup=False, **kw):
+        """The posterior of ``density``, a ``Chi2PipelineDensity``, reweighted to the alternative data vectors ``y_new``
+        (``bayesfast_amd.utils.data_reweight``: a ``Reweighted``) at the original-space draws that ``get(since_iter, include_warmup,
+        flatten=False)`` selects, read where ``sample()`` left them; ``kw`` is ``chunk_bytes``.  Device parts only; single process
+        only, as ``data_loo``."""
+        from ..utils.reweight import data_reweight
+        return data_reweight(density, self._diag_input(since_iter, include_warmup, True, 'samples'), y_new, log_weights=log_weights, **kw)
+
     def profile(self, density, since_iter=None, include_warmup=False, **kw):
         """Profiles (``bayesfast_amd.utils.profile``: a ``Profile``) of ``density``, a ``SurrogateDensity`` or ``Chi2PipelineDensity``:
         the maximisation starts at the posterior mean of the sampling-space draws that ``get(since_iter, include_warmup,

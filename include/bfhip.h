@@ -38,7 +38,8 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_TREEDEPTH 12
 
 /* 112: bfhip_profile_lines and bfhip_pipeline_profile_lines, profiles of the density along grid lines: the device Newton maximiser
- * with coordinates held fixed, walked outward in continuation (additions only).
+ * with coordinates held fixed, walked outward in continuation (additions only).  bfhip_rw_finish (and bfhip_rw_work_bytes), the
+ * posterior reweighted to a batch of columns of log ratios after the first two bfhip_ploo_* stages (additions only: the number stays).
  * 111: bfhip_ploo_moments / _tail / _finish (and bfhip_ploo_work_bytes), pointwise PSIS-LOO and WAIC of a batch of columns of pointwise log
  * likelihoods with a top-M radix select in place of a sort per column (additions only).
  * 110: bfhip_polymodel_columns, a batch of the uploaded polymodel's outputs at draws read in place from the (chain, time, dimension)
@@ -673,6 +674,40 @@ int bfhip_ploo_tail(bfhip_ctx *ctx, long n, const double *series, long ld, int n
                     const double *out, uint64_t *tail_keys, uint32_t *tail_idx, void *work, size_t work_bytes);
 int bfhip_ploo_finish(bfhip_ctx *ctx, long n, const double *series, long ld, int nb, int mode, const double *c, const double *lb,
                       const uint64_t *tail_keys, const uint32_t *tail_idx, double *out, void *work, size_t work_bytes);
+
+/* The posterior reweighted to a batch of nb <= BFHIP_DIAG_BATCH columns of log ratios l (bayesfast_amd/utils/reweight.py has the
+ * definitions): a third stage in place of bfhip_ploo_finish.  The series buffer holds -l in mode BFHIP_PLOO_ELL, so that the ratio of
+ * bfhip_ploo_moments and bfhip_ploo_tail, lb - ell, is r = lb + l; out, tail_keys and tail_idx are what those two stages left (out is
+ * only read), work their work buffer.  The fit and the smoothed tail are launched exactly as bfhip_ploo_finish launches them: khat,
+ * sigma, the cut and the flags are its figures, bit for bit.
+ *   draws    read in place as bfhip_wstat_columns reads them: series row s is draw (s / n_draw, s % n_draw), parameter j at
+ *            x[(s / n_draw) ldw + (since + s % n_draw) ldr + j], float64 or float32 (is_f32); n_chain n_draw == n, ldr >= d, 1 <= d <= BFHIP_MAX_DIM
+ *   centre   (d,) device doubles c: the sums are taken about it
+ *   rw_out   (BFHIP_RW_NOUT(d), BFHIP_DIAG_BATCH) doubles: rows BFHIP_RW_LER ... below, then from row BFHIP_RW_SUMS on the 1 + 2 d sums
+ *            sum e, sum e (x_j - c_j) (j < d), sum e (x_j - c_j)^2 (j < d), and the same 1 + 2 d with e^2, for e = exp(v) of the smoothed
+ *            shifted ratios v (the caller normalises: w = e / sum e).  Columns nb .. are not written.
+ *   rw_work  bfhip_rw_work_bytes(n, d) bytes of the caller's, 256-byte aligned
+ * Rows not above the cut pair go through one pass on the FP64 matrix cores (v_mfma_f64_16x16x4_f64, four rows a step: e of the sixteen
+ * columns against [1, x - c, (x - c)^2] in tiles of 16), the M tail rows are fetched by index with their smoothed values.  A row with
+ * lb = -inf is in no sum of rw_out's rows from BFHIP_RW_SUMS on (where the tail holds such rows they stay in the sum e and sum e^2 behind
+ * BFHIP_RW_LER and BFHIP_RW_ESS, as in bfhip_ploo_finish) and is not read as a number; a non-finite
+ * draw in any other row makes that parameter's sums non-finite in every column.  With flag 1 or 4 every figure of the column but M and the
+ * flags is NaN.  Every reduction has an order fixed by n and d alone, no atomics, and a column never meets its neighbours: bitwise
+ * repeatable, whichever slot or batch a column lands in.  Stream-ordered, no host synchronisation. */
+#define BFHIP_RW_LER 0        /* max r + log sum e over every row: the log of the ratio of the evidences */
+#define BFHIP_RW_KHAT 1
+#define BFHIP_RW_SIGMA 2
+#define BFHIP_RW_M 3
+#define BFHIP_RW_ESS 4        /* (sum e)^2 / sum e^2 over every row */
+#define BFHIP_RW_FLAGS 5      /* as BFHIP_PLOO_FLAGS */
+#define BFHIP_RW_CUT 6
+#define BFHIP_RW_SUMS 8
+#define BFHIP_RW_NOUT(d) (BFHIP_RW_SUMS + 2 * (1 + 2 * (d)))
+size_t bfhip_rw_work_bytes(long n, int d);
+int bfhip_rw_finish(bfhip_ctx *ctx, long n, const double *series, long ld, int nb, int mode, const double *c, const double *lb,
+                    const uint64_t *tail_keys, const uint32_t *tail_idx, const double *out, void *work, size_t work_bytes, int n_chain,
+                    long n_draw, long ldw, long ldr, const void *x, int is_f32, long since, int d, const double *centre, double *rw_out,
+                    void *rw_work, size_t rw_work_bytes);
 
 /* Marginal posterior histograms and credible levels of (weighted) draws (bayesfast_amd/utils/marginals.py has the definitions), on a
  * batch of at most BFHIP_DIAG_BATCH parameters in a (n, BFHIP_DIAG_BATCH) series buffer as bfhip_wstat_columns writes it with w = NULL.
