@@ -139,6 +139,9 @@ SYMBOLS = {
     'bfhip_rw_work_bytes': (C.c_size_t, [C.c_long, C.c_int]),
     'bfhip_rw_finish': (C.c_int, [_vp, C.c_long, _vp, C.c_long, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_int, C.c_long,
                                   C.c_long, C.c_long, _vp, C.c_int, C.c_long, C.c_int, _vp, _vp, _vp, C.c_size_t]),
+    'bfhip_igamc': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp]),
+    'bfhip_lgo_accum': (C.c_int, [_vp, C.c_long, _vp, C.c_long, C.c_int, C.POINTER(C.c_int), _dp, C.c_uint, _vp, C.c_long]),
+    'bfhip_lgo_finish': (C.c_int, [_vp, C.c_long, _vp, C.c_long, C.c_int, _dp, _dp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t]),
     'bfhip_marg_quantise':(C.c_int, [_vp, C.c_long, _vp, C.c_int, _vp, _vp]),
     'bfhip_marg_extent': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
     'bfhip_marg_hist1d': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
@@ -169,6 +172,7 @@ LOO_SSE, LOO_PRESS, LOO_MAX, LOO_ARGMAX, LOO_SY, LOO_SYY, LOO_NUNIT = range(7)  
 PLOO_ELL, PLOO_Z, PLOO_NOUT = 0, 1, 16   # BFHIP_PLOO_ELL / _Z / _NOUT
 PLOO_ROWS = ('lpd', 'swe', 'waic', 'elpd_loo', 'khat', 'sigma', 'n_tail', 'cut', 'ess_loo', 'pit', 'max_r', 'flags', 'sw2', 'max_b')   # BFHIP_PLOO_LPD ...
 RW_ROWS = ('log_evidence_ratio', 'khat', 'sigma', 'n_tail', 'ess', 'flags', 'cut')   # BFHIP_RW_LER ...
+LGO_ROWS = ('chi2_base', 'chi2_lgo', 'ppp_base', 'ppp_lgo')   # BFHIP_LGO_CHI2_BASE ...; BFHIP_LGO_NOUT rows
 RW_SUMS = 8            # BFHIP_RW_SUMS: the out block's first row of sums; BFHIP_RW_NOUT(d) = RW_SUMS + 2 (1 + 2 d) rows
 WSTAT_TILE = 2048      # sorted positions per workgroup of bfhip_wstat_cumweights: its work buffer is ceil(n / 2048) doubles
 

@@ -366,6 +366,12 @@ class Chi2PipelineDensity(SurrogateDensity):
         from ..utils.data_loo import data_loo
         return data_loo(self, x, **kw)
 
+    def data_lgo(self, x, groups, **kw):
+        """Leave-group-out cross-validation of groups of data points at the ORIGINAL-space draws x, a GPU tensor (n_chain, n_draw, d)
+        or (n, d): ``bayesfast_amd.utils.data_lgo(self, x, groups, **kw)``, a ``DataLGO``."""
+        from ..utils.data_lgo import data_lgo
+        return data_lgo(self, x, groups, **kw)
+
     def data_reweight(self, x, y_new, **kw):
         """The posterior reweighted to the alternative data vectors y_new (K, m) or (m,) at the ORIGINAL-space draws x, a GPU tensor
         (n_chain, n_draw, d) or (n, d): ``bayesfast_amd.utils.data_reweight(self, x, y_new, **kw)``, a ``Reweighted``."""

@@ -510,3 +510,4 @@ extern "C" int bfhip_wstat_quantiles(bfhip_ctx *ctx, long n, const uint64_t *key
 // ==== pointwise PSIS-LOO and WAIC of a batch of columns ==============================================================================
 #include "bfhip_ploo.h"
 #include "bfhip_rw.h"
+#include "bfhip_lgo.h"

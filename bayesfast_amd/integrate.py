@@ -292,6 +292,9 @@ def reference_classes(bayesfast=None):
         def data_loo(self, *args, **kwargs):
             return self._inner.data_loo(*args, **kwargs)
 
+        def data_lgo(self, *args, **kwargs):
+            return self._inner.data_lgo(*args, **kwargs)
+
         def data_reweight(self, *args, **kwargs):
             return self._inner.data_reweight(*args, **kwargs)
 

@@ -490,6 +490,13 @@ class TraceTuple:
         from ..utils.data_loo import data_loo
         return data_loo(density, self._diag_input(since_iter, include_warmup, True, 'samples'), log_weights=log_weights, **kw)
 
+    def data_lgo(self, density, groups, log_weights=None, since_iter=None, include_warmup=False):
+        """Leave-group-out cross-validation (``bayesfast_amd.utils.data_lgo``: a ``DataLGO``) of the groups of data points ``groups`` of
+        ``density``, a ``Chi2PipelineDensity``, at the original-space draws that ``get(since_iter, include_warmup, flatten=False)``
+        selects, read where ``sample()`` left them.  Device parts only; single process only, as ``data_loo``."""
+        from ..utils.data_lgo import data_lgo
+        return data_lgo(density, self._diag_input(since_iter, include_warmup, True, 'samples'), groups, log_weights=log_weights)
+
     def data_reweight(self, density, y_new, log_weights=None, since_iter=None, include_warmup=False, **kw):
         """The posterior of ``density``, a ``Chi2PipelineDensity``, reweighted to the alternative data vectors ``y_new``
         (``bayesfast_amd.utils.data_reweight``: a ``Reweighted``) at the original-space draws that ``get(since_iter, include_warmup,

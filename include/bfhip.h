@@ -40,6 +40,8 @@ typedef struct bfhip_ctx bfhip_ctx;
 /* 112: bfhip_profile_lines and bfhip_pipeline_profile_lines, profiles of the density along grid lines: the device Newton maximiser
  * with coordinates held fixed, walked outward in continuation (additions only).  bfhip_rw_finish (and bfhip_rw_work_bytes), the
  * posterior reweighted to a batch of columns of log ratios after the first two bfhip_ploo_* stages (additions only: the number stays).
+ * bfhip_lgo_accum and bfhip_lgo_finish, leave-group-out cross-validation around the same two stages, and bfhip_igamc, the regularised
+ * upper incomplete gamma function (additions only: the number stays).
  * 111: bfhip_ploo_moments / _tail / _finish (and bfhip_ploo_work_bytes), pointwise PSIS-LOO and WAIC of a batch of columns of pointwise log
  * likelihoods with a top-M radix select in place of a sort per column (additions only).
  * 110: bfhip_polymodel_columns, a batch of the uploaded polymodel's outputs at draws read in place from the (chain, time, dimension)
@@ -708,6 +710,38 @@ int bfhip_rw_finish(bfhip_ctx *ctx, long n, const double *series, long ld, int n
                     const uint64_t *tail_keys, const uint32_t *tail_idx, const double *out, void *work, size_t work_bytes, int n_chain,
                     long n_draw, long ldw, long ldr, const void *x, int is_f32, long since, int d, const double *centre, double *rw_out,
                     void *rw_work, size_t rw_work_bytes);
+
+/* Leave-group-out cross-validation of a batch of nb <= BFHIP_DIAG_BATCH groups of data points (bayesfast_amd/utils/data_lgo.py has the
+ * definitions).  A group's column of the (n, BFHIP_DIAG_BATCH) series buffer holds ell_s = c - q_s / 2, q_s the conditional chi-square
+ * of the group's dof points given the rest at draw s; bfhip_ploo_moments and bfhip_ploo_tail run on it in mode BFHIP_PLOO_ELL.
+ * bfhip_igamc: out[i] = Q(a[i], x[i]), the regularised upper incomplete gamma function (the chi-square survival function
+ *   Q(dof / 2, q / 2)), a, x, out (n,) device doubles: a series below max(a, 1), a continued fraction above, at most 5000 terms; Q(a, 0)
+ *   = 1, Q(a, inf) = 0, NaN for a NaN argument, a <= 0 or x < 0.
+ * bfhip_lgo_accum: folds the (n, nb) buffer z (element (s, j) at z[s ldz + j], ldz >= nb) of whitened residuals into acc (element (s,
+ *   slot) at acc[s lda + slot], lda >= BFHIP_DIAG_BATCH): column j goes to slot slot[j] (HOST array of nb ints; -1: to none), and the
+ *   running value of (row, slot) is updated once per column in column order as acc = acc - 0.5 * (z * z), never contracted.  A slot
+ *   whose bit of start is set starts in this call from c[slot] (HOST array of BFHIP_DIAG_BATCH doubles; may be NULL when start is 0),
+ *   whatever acc holds; the other slots go on from what acc holds.  Slots that neither start nor take a column are not touched.  The
+ *   bits of a column therefore depend on the order of its z columns alone, not on how they were split over calls, slots or batches.
+ *   Rows are read and written two doubles at a time where both strides are even and both bases 16-byte aligned.  No atomics.
+ * bfhip_lgo_finish: the third stage in place of bfhip_ploo_finish.  c, dof: HOST arrays of nb doubles, dof > 0.  The fit and the
+ *   smoothed tail are launched exactly as bfhip_ploo_finish launches them and out gets bfhip_ploo_finish's rows (BFHIP_PLOO_PIT is
+ *   NaN); lgo_out (BFHIP_LGO_NOUT, BFHIP_DIAG_BATCH) doubles gets, with q = max(2 (c - ell), 0) and Q = Q(dof / 2, q / 2), the rows below,
+ *   in one pass over the rows plus the M tail rows fetched by index.  A row with lb = -inf is not read as a number and is in no sum
+ *   but, where the tail holds such rows, in the normalisation of the smoothed weights and in BFHIP_PLOO_ESS, as in bfhip_ploo_finish.
+ *   With flag 1 or 4 every figure of the column but M and the flags is NaN.  work: bfhip_ploo_work_bytes(n) bytes, the two stages'.
+ * n > 2^31 - 1: BFHIP_ERR_UNSUPPORTED.  Every reduction has an order fixed by n alone and a column never meets its neighbours: bitwise
+ * repeatable, whichever slot or batch a column lands in.  Stream-ordered, no host synchronisation. */
+#define BFHIP_LGO_NOUT 4
+#define BFHIP_LGO_CHI2_BASE 0   /* sum w q, w = exp(lb) */
+#define BFHIP_LGO_CHI2 1        /* sum exp(v) q under the smoothed, normalised weights */
+#define BFHIP_LGO_PPP_BASE 2    /* sum w Q */
+#define BFHIP_LGO_PPP 3         /* sum exp(v) Q */
+int bfhip_igamc(bfhip_ctx *ctx, long n, const double *a, const double *x, double *out);
+int bfhip_lgo_accum(bfhip_ctx *ctx, long n, const double *z, long ldz, int nb, const int *slot, const double *c, unsigned start,
+                    double *acc, long lda);
+int bfhip_lgo_finish(bfhip_ctx *ctx, long n, const double *series, long ld, int nb, const double *c, const double *dof, const double *lb,
+                     const uint64_t *tail_keys, const uint32_t *tail_idx, double *out, double *lgo_out, void *work, size_t work_bytes);
 
 /* Marginal posterior histograms and credible levels of (weighted) draws (bayesfast_amd/utils/marginals.py has the definitions), on a
  * batch of at most BFHIP_DIAG_BATCH parameters in a (n, BFHIP_DIAG_BATCH) series buffer as bfhip_wstat_columns writes it with w = NULL.
