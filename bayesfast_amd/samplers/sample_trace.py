@@ -545,6 +545,43 @@ class TraceTuple:
             raise NotImplementedError('pairs of more than %d parameters on the device route.' % _lib.MARG_MAX_LD)
         return marginals_sharded(_make_passes(x, given, kind, checked[3], d_all), *checked)
 
+    def kde(self, log_weights=None, since_iter=None, include_warmup=False, original_space=True, params=None, **kw):
+        """The kernel density estimate (``bayesfast_amd.utils.kde``) of the draws that ``get(since_iter, include_warmup,
+        original_space, flatten=True)`` selects, built where ``sample()`` left them (device parts take the device route);
+        ``log_weights``, if given, holds one log weight per selected draw, shaped (n_chain, n_t) or flat in that order; ``params``
+        selects parameters by index; ``kw`` are ``bw_method`` and ``bw_factor``.  Single process only: with more than one rank it
+        raises ``NotImplementedError``."""
+        from .. import parallel
+        from ..utils.kde import kde
+        if parallel.world()[1] > 1:
+            raise NotImplementedError('the estimate is built from the draws of ALL chains, and this TraceTuple holds one rank\'s: '
+                                      'gather the chains and use the host port, utils.kde(tt.gather().get(flatten=True)).')
+        x = self._diag_input(since_iter, include_warmup, original_space, 'samples')
+        x = x.reshape((-1, x.shape[-1]))
+        if params is not None:
+            x = x[:, [int(p) for p in params]]
+        if log_weights is not None:
+            log_weights = log_weights.reshape(-1)
+        return kde(x, log_weights=log_weights, **kw)
+
+    def parameter_shift(self, other, log_weights=None, log_weights_other=None, since_iter=None, include_warmup=False,
+                        original_space=True, **kw):
+        """The parameter-difference test (``bayesfast_amd.utils.parameter_shift``: a ``ParameterShift``) between the draws that
+        ``get(since_iter, include_warmup, original_space, flatten=True)`` selects here and those of ``other``: another
+        ``TraceTuple`` (the same selection is applied to it) or a tensor or array of draws (n, d).  ``kw`` are ``params``,
+        ``n_pairs``, ``bw_method``, ``bw_factor``, ``loo`` and ``seed``.  The two chains are assumed independent.  Single
+        process only: with more than one rank it raises ``NotImplementedError``."""
+        from .. import parallel
+        from ..utils.shift import parameter_shift
+        if parallel.world()[1] > 1:
+            raise NotImplementedError('the difference sample pairs the draws of ALL chains, and this TraceTuple holds one rank\'s: '
+                                      'gather the chains and use the host port, '
+                                      'utils.parameter_shift(tt.gather().get(flatten=True), other.gather().get(flatten=True)).')
+        x = self._diag_input(since_iter, include_warmup, original_space, 'samples')
+        if isinstance(other, TraceTuple):
+            other = other._diag_input(since_iter, include_warmup, original_space, 'samples')
+        return parameter_shift(x, other, log_weights_a=log_weights, log_weights_b=log_weights_other, **kw)
+
     def __getitem__(self, key):
         return self.sample_traces[key]
 

@@ -37,7 +37,9 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_DIM 128         /* input_size limit of the device path */
 #define BFHIP_MAX_TREEDEPTH 12
 
-/* 112: bfhip_profile_lines and bfhip_pipeline_profile_lines, profiles of the density along grid lines: the device Newton maximiser
+/* 113: bfhip_kde_logsum (and bfhip_kde_work_bytes), the pairwise log-sum-exp of Gaussian kernels behind the multivariate kernel density
+ * estimate and the parameter-shift test (additions only).
+ * 112: bfhip_profile_lines and bfhip_pipeline_profile_lines, profiles of the density along grid lines: the device Newton maximiser
  * with coordinates held fixed, walked outward in continuation (additions only).  bfhip_rw_finish (and bfhip_rw_work_bytes), the
  * posterior reweighted to a batch of columns of log ratios after the first two bfhip_ploo_* stages (additions only: the number stays).
  * bfhip_lgo_accum and bfhip_lgo_finish, leave-group-out cross-validation around the same two stages, and bfhip_igamc, the regularised
@@ -466,6 +468,25 @@ int bfhip_importance_weights(bfhip_ctx *ctx, long n, const double *logp, const d
  * pts (d,m), out (d,m).  SIT._gaussianize_1d (transforms/sit.py:223-227) applies norm.ppf to it at the spline knots. */
 int bfhip_kde_cdf(bfhip_ctx *ctx, int d, long n, const double *data, const double *w, const double *h, int m, const double *pts,
                   double *out);
+
+/* The pairwise sum of a multivariate Gaussian kernel density estimate (utils/kde.py:265-320 of the reference, its pdf and logpdf
+ * without the d x d whitening and the normalisation, which stay with the caller):
+ *     out[i] = log sum_j exp(logw[j] - |zq_i - z_j|^2 / 2),   i < m, j < n,
+ * a true log-sum-exp: a query far from every data row has a finite result where the density itself underflows.
+ *   z (n rows), zq (m rows): WHITENED and centred float64 rows of d values, row strides ldz, ldq >= d.
+ *   logw (n) or NULL (all zero).  A -inf entry is a row that is no part of the sample, whatever it holds.
+ *   exclude_self: the term j == i is left out (the leave-self-out density at the data rows); needs zq == z, ldq == ldz, m == n.
+ *   work: bfhip_kde_work_bytes(n, m, d) bytes of the caller's, 256-byte aligned (0: arguments that bfhip_kde_logsum refuses).
+ * Energies are (|zq_i|^2 + |z_j|^2) / 2 - zq_i . z_j with the dot products on the float64 matrix cores.  The data rows are cut into
+ * parts by n alone and every sum has an order fixed by (n, d): a query's result depends on that query and the data only -- bit for
+ * bit the same alone, in any batch, at any offset -- and few queries still spread over the device.  No atomics; stream-ordered, no
+ * host synchronisation.  A NaN in a query row makes that output NaN and no other; a NaN or an infinity in a data row of weight above
+ * -inf, or a NaN or +inf in logw, makes every output NaN.  Every weight -inf: every output -inf.
+ * BFHIP_ERR_ARG: n, m or d < 1, a stride below d, exclude_self on other queries, a small work buffer.  BFHIP_ERR_UNSUPPORTED:
+ * d > BFHIP_MAX_DIM; n or m > 2^31 - 1. */
+size_t bfhip_kde_work_bytes(long n, long m, int d);
+int bfhip_kde_logsum(bfhip_ctx *ctx, int d, long n, const double *z, long ldz, const double *logw, long m, const double *zq, long ldq,
+                     int exclude_self, double *out, void *work, size_t work_bytes);
 
 /* The normal quantile function of n probabilities, out[i] = ndtri(p[i]) (scipy.special.ndtri, which scipy.stats.norm.ppf evaluates:
  * utils/sobol.py:57 on the Sobol points of multivariate_normal, transforms/sit.py:225 on the KDE cdfs): Cephes' algorithm; -inf / +inf
