@@ -564,6 +564,50 @@ class TraceTuple:
             log_weights = log_weights.reshape(-1)
         return kde(x, log_weights=log_weights, **kw)
 
+    def modes(self, log_weights=None, since_iter=None, include_warmup=False, original_space=True, per_chain=4, **kw):
+        """The modes (``bayesfast_amd.utils.modes``: a ``Modes``) of the kernel density estimate of the draws that ``get(since_iter,
+        include_warmup, original_space, flatten=True)`` selects, and which chains sit in which.  The mean-shift seeds are
+        ``per_chain`` evenly spaced draws of every chain; with ``log_weights`` ((n_chain, n_t) or flat in that order) a chain's
+        ``per_chain`` seeds are resampled within the chain in proportion to the weights.  ``kw`` are ``params``, ``bw_method``,
+        ``bw_factor``, ``tol``, ``max_iter``, ``merge_tol``, ``min_share`` and ``seed``.  The result also has ``chain_mode``
+        (n_chain,), the majority label of the chain's seeds (ties to the lower label), and ``chain_split`` (n_chain,), whether its
+        seeds disagree.  Single process only: with more than one rank it raises ``NotImplementedError``."""
+        from .. import parallel
+        from ..utils.kde import kde, _host
+        from ..utils.modes import modes_from_seeds, systematic_rows
+        if parallel.world()[1] > 1:
+            raise NotImplementedError('the modes are those of the draws of ALL chains, and this TraceTuple holds one rank\'s: '
+                                      'gather the chains and use the host port, utils.modes(tt.gather().get(flatten=True)).')
+        x = self._diag_input(since_iter, include_warmup, original_space, 'samples')
+        n_chain, n_t, per_chain = int(x.shape[0]), int(x.shape[1]), int(per_chain)
+        if per_chain < 1:
+            raise ValueError('per_chain should be at least 1.')
+        x = x.reshape((-1, x.shape[-1]))
+        params, seed = kw.pop('params', None), kw.pop('seed', 0)
+        if params is not None:
+            x = x[:, [int(p) for p in params]]
+        if log_weights is not None:
+            log_weights = log_weights.reshape(-1)
+        est = kde(x, log_weights=log_weights, bw_method=kw.pop('bw_method', None), bw_factor=kw.pop('bw_factor', None))
+        if log_weights is None:
+            t = ((np.arange(per_chain) + 0.5) * n_t / per_chain).astype(np.int64)
+            rows = (np.arange(n_chain)[:, None] * n_t + t[None, :]).reshape(-1)
+        else:
+            rng = np.random.default_rng(seed)
+            w = _host(est.weights).reshape(n_chain, n_t)
+            rows = np.concatenate([c * n_t + (systematic_rows(w[c], per_chain, rng) if w[c].sum() > 0. else np.zeros(per_chain, np.int64))
+                                   for c in range(n_chain)])
+        out = modes_from_seeds(est, rows, **kw)
+        label = out.label.reshape(n_chain, per_chain)
+        out.chain_mode = np.full(n_chain, -1, dtype=np.int64)
+        out.chain_split = np.zeros(n_chain, dtype=bool)
+        for c in range(n_chain):
+            got = label[c][label[c] >= 0]
+            if got.size:
+                out.chain_mode[c] = int(np.argmax(np.bincount(got)))     # the first of equal counts: the lower label
+                out.chain_split[c] = bool(np.any(got != got[0]))
+        return out
+
     def parameter_shift(self, other, log_weights=None, log_weights_other=None, since_iter=None, include_warmup=False,
                         original_space=True, **kw):
         """The parameter-difference test (``bayesfast_amd.utils.parameter_shift``: a ``ParameterShift``) between the draws that

@@ -11,8 +11,9 @@ from .laplace import Laplace, LaplaceResult, make_positive
 from .profile import profile, Profile, ProfileInterval
 from .kde import kde
 from .shift import parameter_shift, ParameterShift
+from .modes import modes, Modes
 
 __all__ = ['SystematicResampler', 'integrated_time', 'AutocorrError', 'Laplace', 'LaplaceResult', 'make_positive', 'rhat', 'ess', 'summary',
            'psis', 'PSISResult', 'weighted_summary', 'marginals', 'Marginals', 'predictive', 'Predictive', 'data_loo',
            'pointwise_loo', 'DataLOO', 'reweight_moments', 'data_reweight', 'Reweighted', 'profile', 'Profile', 'ProfileInterval',
-           'data_lgo', 'grouped_loo', 'group_whitening_of', 'DataLGO', 'kde', 'parameter_shift', 'ParameterShift']
+           'data_lgo', 'grouped_loo', 'group_whitening_of', 'DataLGO', 'kde', 'parameter_shift', 'ParameterShift', 'modes', 'Modes']

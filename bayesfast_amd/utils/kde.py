@@ -31,10 +31,18 @@ A GPU tensor as ``dataset`` takes the device route: mean, covariance, Cholesky f
 one (n, d) product), the pairwise sum through ``bfhip_kde_logsum`` (csrc/bfhip_kde.h: float64 matrix cores, a running-maximum
 log-sum-exp, an order of summation fixed by (n, d), so a query gives the same bits alone and in any batch).  Queries may be
 tensors or arrays, results are device tensors.  At most ``BFHIP_MAX_DIM`` dimensions and 2^31 - 1 rows.  NumPy arrays and CPU
-tensors take a host port of the same arithmetic, chunked over the queries so that memory stays bounded."""
+tensors take a host port of the same arithmetic, chunked over the queries so that memory stays bounded.
+
+Kernel-weighted means.  The same pairs answer a second question: with p_ij = w_j exp(-|zq_i - z_j|^2 / 2) / sum_j' (the same), the
+average sum_j p_ij v_j of any per-row quantity v over the rows near a query (``kde_wmean`` / ``bfhip_kde_wmean`` on the device,
+``_wmean_host`` on the host, one pass either way).  Three methods are this sum with a different v:
+
+  grad_logpdf(x)   the score of the estimate, A (sum_j p_ij z_j - zq_i) with v = z
+  regress(values)  Nadaraya-Watson kernel regression E[values | x]; with ``loo=True`` the cross-validated prediction at the rows
+  mean_shift(x0)   the iteration zq <- sum_j p_ij z_j, which climbs to a mode of the estimate (``utils/modes.py`` builds on it)"""
 import numpy as np
 
-__all__ = ['kde', 'kde_logsum']
+__all__ = ['kde', 'kde_logsum', 'kde_wmean']
 
 _HOST_CHUNK_BYTES = 1 << 27    # the host port's (queries x data) block of energies
 
@@ -101,6 +109,78 @@ def kde_logsum(z, logw, zq, exclude_self=False):
         _lib.check(ctx._lib.bfhip_kde_logsum(ctx.handle, d, n, _ptr(z), ldz, _ptr(logw), m, _ptr(zq), ldq, int(bool(exclude_self)),
                                              _ptr(out), _ptr(work), work.numel()))
     return out
+
+
+# ---- the kernel-weighted means: mean[i] = sum_j p_ij v_j, p_ij = softmax_j(logw[j] - |zq_i - z_j|^2 / 2) ----------------------------------
+def _wmean_host(z, logw, zq, v, exclude_self=False):
+    """The host port of ``bfhip_kde_wmean``: (logsum (m,), mean (m, k)) for ``v`` (n, k).  Rows of weight -inf are no part of the
+    sample whatever ``z`` and ``v`` hold there; a query with no term has logsum -inf and a NaN mean."""
+    n, m = z.shape[0], zq.shape[0]
+    with np.errstate(all='ignore'):
+        off = logw == -np.inf
+        if off.any():
+            z = np.where(off[:, None], 0., z)
+            v = np.where(off[:, None], 0., v)
+        c = logw - 0.5 * np.einsum('ij,ij->i', z, z)
+        c = np.where(off, -np.inf, np.where(np.isfinite(c), c, np.nan))   # a bad weight or row poisons every output, as kd_rows_kernel has it
+        logsum, mean = np.empty(m), np.empty((m, v.shape[1]))
+        step = max(1, _HOST_CHUNK_BYTES // (8 * n))
+        for lo in range(0, m, step):
+            q = zq[lo:lo + step]
+            t = q @ z.T
+            t += c[None, :]
+            t -= 0.5 * np.einsum('ij,ij->i', q, q)[:, None]
+            if exclude_self:
+                t[np.arange(q.shape[0]), np.arange(lo, lo + q.shape[0])] = -np.inf
+            top = t.max(axis=1)
+            top = np.where(np.isfinite(top), top, 0.)
+            np.exp(t - top[:, None], out=t)
+            s = t.sum(axis=1)
+            logsum[lo:lo + step] = top + np.log(s)
+            num = t @ v
+            mean[lo:lo + step] = np.where(np.isfinite(num), num / s[:, None], np.nan)    # a bad value: NaN, whether p inf or 0 inf
+    return logsum, mean
+
+
+def kde_wmean(z, logw, zq, v, exclude_self=False):
+    """``bfhip_kde_wmean`` on device tensors: (logsum (m,), mean (m, k)), mean[i] = sum_j p_ij v[j] with p_ij the normalised
+    kernel weights of query i.  ``z``, ``logw``, ``zq`` and ``exclude_self`` as in ``kde_logsum``; ``v`` (n, k) is a float64
+    device matrix with unit stride along a row, and may be ``z`` itself (nothing more is staged then).  More than
+    ``BFHIP_MAX_DIM`` columns are taken in batches."""
+    import torch
+    from .. import _lib
+    from ..device import get_context, _ptr
+    for t in (z, zq, v):
+        if t.dtype != torch.float64 or t.ndim != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or not t.is_cuda:
+            raise ValueError('z, zq and v should be float64 device matrices with unit stride along a row.')
+    if z.shape[1] != zq.shape[1]:
+        raise ValueError('z and zq should have the same number of columns.')
+    if v.shape[0] != z.shape[0] or v.shape[1] < 1 or v.device != z.device:
+        raise ValueError('v should have one row per row of z, at least one column, and live on the device of z.')
+    n, d = z.shape
+    m, k = zq.shape[0], v.shape[1]
+    ldz = z.stride(0) if n > 1 else max(d, 1)
+    ldq = zq.stride(0) if m > 1 else max(d, 1)
+    ldv = v.stride(0) if n > 1 else max(k, 1)
+    if v.data_ptr() == z.data_ptr() and k == d:
+        ldv = ldz
+    if exclude_self:
+        if zq.data_ptr() != z.data_ptr() or m != n:
+            raise ValueError('exclude_self needs zq to be z.')
+        ldq = ldz
+    if logw is not None:
+        if logw.dtype != torch.float64 or logw.shape != (n,) or not logw.is_contiguous() or logw.device != z.device:
+            raise ValueError('logw should be a contiguous float64 vector of length n on the device of z.')
+    with torch.cuda.device(z.device):
+        ctx = get_context(z.device.index)
+        logsum, mean = ctx.empty((m,)), ctx.empty((m, k))
+        for c0 in range(0, k, _lib.MAX_DIM):
+            kc = min(_lib.MAX_DIM, k - c0)
+            nbytes = ctx._lib.bfhip_kde_wmean_work_bytes(n, m, d, kc)
+            work = ctx.empty((max(int(nbytes), 256),), dtype=torch.uint8)
+            _lib.check(ctx._lib.bfhip_kde_wmean(ctx.handle, d, n, _ptr(z), ldz, _ptr(logw), kc, _ptr(v[:, c0:]), ldv, m, _ptr(zq), ldq,
+                                                int(bool(exclude_self)), _ptr(logsum), _ptr(mean[:, c0:]), k, _ptr(work), work.numel()))
+    return logsum, mean
 
 
 class kde:
@@ -308,6 +388,78 @@ class kde:
         s = _logsum_host(self._z, self._logw, self._z, exclude_self=True)
         with np.errstate(all='ignore'):
             return np.where(self._weights >= 1., -np.inf, s - np.log1p(-self._weights) - self._log_norm)
+
+    # ---- kernel-weighted means ----------------------------------------------------------------------------------------------------------
+    def _wmean(self, zq, v, exclude_self=False):
+        if self._dev:
+            return kde_wmean(self._z, self._logw, self._z if exclude_self else zq.contiguous(), v, exclude_self)
+        return _wmean_host(self._z, self._logw, zq, v, exclude_self)
+
+    def grad_logpdf(self, x):
+        """The score of the estimate, the gradient of ``logpdf`` at the points ``x`` in the original coordinates: (m, d)."""
+        zq = self._whiten(self._points(x))
+        return (self._wmean(zq, self._z)[1] - zq) @ self._white.T
+
+    def regress(self, values, x=None, loo=False):
+        """Kernel regression (Nadaraya-Watson) of one value (n,) or k values (n, k) per row: E[values | x] at the points ``x``, (m,)
+        or (m, k); ``x=None`` means at the data rows.  ``loo=True`` needs ``x=None`` and leaves each row's own kernel out, which is
+        the cross-validated prediction that picks a bandwidth; a row of weight 1 gives NaN.  Rows of zero weight carry no value,
+        whatever ``values`` holds there."""
+        if self._dev:
+            import torch
+            v = torch.as_tensor(values.detach() if hasattr(values, 'detach') else np.asarray(values, dtype=np.float64),
+                                device=self.dataset.device).to(torch.float64)
+        else:
+            v = np.asarray(_host(values), dtype=np.float64)
+        flat = v.ndim == 1
+        if flat:
+            v = v[:, None]
+        if v.ndim != 2 or v.shape[0] != self.n or v.shape[1] < 1:
+            raise ValueError("`values` should hold one value, or one row of values, per row of the dataset.")
+        if loo and x is not None:
+            raise ValueError('loo=True predicts at the data rows: x should be None.')
+        if self._dev:
+            v = v.contiguous()
+        zq = self._z if x is None else self._whiten(self._points(x))
+        out = self._wmean(zq, v, exclude_self=bool(loo))[1]
+        return out[:, 0] if flat else out
+
+    def _mean_shift_white(self, zq, tol, max_iter):
+        """Mean shift of whitened points: (zq, logsum at zq, iterations, converged per point).  The largest step is looked at once
+        per 8 iterations, so the device route synchronises with the host once per 8 kernel calls."""
+        n_iter, max_iter = 0, int(max_iter)
+        step = None
+        while n_iter < max_iter:
+            for _ in range(min(8, max_iter - n_iter)):
+                new = self._wmean(zq, self._z)[1]
+                d = new - zq
+                step = (d * d).sum(1)
+                zq = new
+                n_iter += 1
+            if bool((step < tol * tol).all()):
+                break
+        if self._dev:
+            import torch
+            logsum = kde_logsum(self._z, self._logw, zq.contiguous())
+            conv = step < tol * tol if step is not None else torch.zeros(zq.shape[0], dtype=torch.bool, device=zq.device)
+        else:
+            logsum = _logsum_host(self._z, self._logw, zq)
+            conv = step < tol * tol if step is not None else np.zeros(zq.shape[0], dtype=bool)
+        return zq, logsum, n_iter, conv
+
+    def mean_shift(self, x0, tol=1e-8, max_iter=1000):
+        """Climbs from the points ``x0`` to modes of the estimate by the mean-shift iteration x <- sum_j p_j(x) x_j, which is a
+        gradient ascent of ``logpdf`` with the estimate's own step.  Returns ``(x, logpdf, n_iter, converged)``: the end points
+        (m, d) in the original coordinates, the log density there, the iterations made (all points iterate together) and, per
+        point, whether its last step was below ``tol`` in whitened units.  The rate is linear, about 1 / (1 + factor^2) per
+        iteration near a Gaussian mode, so a very small bandwidth needs thousands of iterations."""
+        zq, logsum, n_iter, conv = self._mean_shift_white(self._whiten(self._points(x0)), float(tol), max_iter)
+        if self._dev:
+            import torch
+            x = torch.linalg.solve_triangular(self._white.T, zq.T, upper=True).T + self._mean
+        else:
+            x = np.linalg.solve(self._white.T, zq.T).T + self._mean
+        return x, logsum - self._log_norm, n_iter, conv
 
     def cdf(self, x):
         """The cumulative distribution at the points ``x`` of a one-dimensional estimate: (m,)."""

@@ -37,7 +37,9 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_DIM 128         /* input_size limit of the device path */
 #define BFHIP_MAX_TREEDEPTH 12
 
-/* 113: bfhip_kde_logsum (and bfhip_kde_work_bytes), the pairwise log-sum-exp of Gaussian kernels behind the multivariate kernel density
+/* 114: bfhip_kde_wmean (and bfhip_kde_wmean_work_bytes), the kernel-weighted means over the pairs of bfhip_kde_logsum: the score of the
+ * estimate, kernel regression and the mean-shift step (additions only).
+ * 113: bfhip_kde_logsum (and bfhip_kde_work_bytes), the pairwise log-sum-exp of Gaussian kernels behind the multivariate kernel density
  * estimate and the parameter-shift test (additions only).
  * 112: bfhip_profile_lines and bfhip_pipeline_profile_lines, profiles of the density along grid lines: the device Newton maximiser
  * with coordinates held fixed, walked outward in continuation (additions only).  bfhip_rw_finish (and bfhip_rw_work_bytes), the
@@ -487,6 +489,27 @@ int bfhip_kde_cdf(bfhip_ctx *ctx, int d, long n, const double *data, const doubl
 size_t bfhip_kde_work_bytes(long n, long m, int d);
 int bfhip_kde_logsum(bfhip_ctx *ctx, int d, long n, const double *z, long ldz, const double *logw, long m, const double *zq, long ldq,
                      int exclude_self, double *out, void *work, size_t work_bytes);
+
+/* Kernel-weighted means over the same pairs, in one pass: with t_ij = logw[j] - |zq_i - z_j|^2 / 2,
+ *     logsum[i] = log sum_j exp(t_ij),   mean[i][c] = sum_j exp(t_ij - logsum[i]) v[j][c],   c < k.
+ * With v = z this is the score of the estimate (grad log p = A (mean - zq_i), A the whitening factor) and the mean-shift step; with
+ * any per-row quantity it is Nadaraya-Watson kernel regression, and with exclude_self its cross-validated prediction at the rows.
+ *   z, logw, zq, exclude_self: as in bfhip_kde_logsum.
+ *   v (n rows of k values, row stride ldv >= k), 1 <= k <= BFHIP_MAX_DIM (batch wider v); v == z (with ldv == ldz, k == d) is allowed
+ *   and is the common case: nothing more is staged then.
+ *   logsum (m) or NULL; mean (m rows of k values, row stride ldo >= k).
+ *   work: bfhip_kde_wmean_work_bytes(n, m, d, k) bytes of the caller's, 256-byte aligned (0: arguments that bfhip_kde_wmean refuses).
+ * The data rows are cut into parts as in bfhip_kde_logsum; a part leaves (maximum, sum, k numerators) per query, merged in increasing
+ * part number; the queries of one launch shrink so that these partials stay below 64 MB, which changes no bit.  Every sum has an
+ * order fixed by (n, d, k): a query gives the same bits alone, in any batch, at any offset.  No atomics; stream-ordered.
+ * A row of weight -inf is no part of the sample, whatever z and v hold there.  A NaN or +inf weight, or a non-finite z row of weight
+ * above -inf, makes every output NaN; a non-finite v[j][c] in such a row makes column c NaN for every query; a NaN in a query row
+ * makes that query's outputs NaN.  A query with no term (exclude_self with one weighted row) has logsum -inf and a NaN mean.
+ * BFHIP_ERR_ARG: n, m, d or k < 1, a null pointer, ldz or ldq < d, ldv or ldo < k, exclude_self on other queries, a small work
+ * buffer.  BFHIP_ERR_UNSUPPORTED: d or k > BFHIP_MAX_DIM; n or m > 2^31 - 1. */
+size_t bfhip_kde_wmean_work_bytes(long n, long m, int d, int k);
+int bfhip_kde_wmean(bfhip_ctx *ctx, int d, long n, const double *z, long ldz, const double *logw, int k, const double *v, long ldv, long m,
+                    const double *zq, long ldq, int exclude_self, double *logsum, double *mean, long ldo, void *work, size_t work_bytes);
 
 /* The normal quantile function of n probabilities, out[i] = ndtri(p[i]) (scipy.special.ndtri, which scipy.stats.norm.ppf evaluates:
  * utils/sobol.py:57 on the Sobol points of multivariate_normal, transforms/sit.py:225 on the KDE cdfs): Cephes' algorithm; -inf / +inf
