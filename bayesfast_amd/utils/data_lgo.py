@@ -53,7 +53,9 @@ carries the posterior: khat > 0.7 says so, and the honest answer then is to samp
 ``ppp_base``."""
 import numpy as np
 
-from .data_loo import _Stages, _host_column, _normalise_device, _normalise_host
+from ._pipeline_data import (base_log_weights, check_density, check_gpu_draws, check_one_process, dense_precision, host_f64, input_map,
+                             shaped_draws, sum_and_se)
+from .data_loo import _Stages, _host_column, _normalise_host
 from .psis import _psis_host
 
 __all__ = ['data_lgo', 'grouped_loo', 'group_whitening_of', 'DataLGO']
@@ -74,12 +76,11 @@ class DataLGO:
         for name in _GROUP:
             setattr(self, name, np.asarray(cols[name], dtype=np.float64))
         self.n_tail = np.asarray(cols['n_tail'], dtype=np.int64)
-        k = len(self.groups)
+        for name in _TOTAL:
+            total, se = sum_and_se(getattr(self, name))
+            setattr(self, name + '_total', total)
+            setattr(self, 'se_' + name, se)
         with np.errstate(all='ignore'):
-            for name in _TOTAL:
-                v = getattr(self, name)
-                setattr(self, name + '_total', float(v.sum()))
-                setattr(self, 'se_' + name, float(np.sqrt(k * v.var(ddof=1))) if k > 1 else float('nan'))
             self.n_khat_bad = int((self.khat > 0.7).sum())
 
     def _same_groups(self, other):
@@ -91,10 +92,7 @@ class DataLGO:
         hold the same groups."""
         if not self._same_groups(other):
             raise ValueError('the two results should hold the same groups.')
-        diff = self.elpd_lgo - other.elpd_lgo
-        k = diff.size
-        with np.errstate(all='ignore'):
-            return float(diff.sum()), (float(np.sqrt(k * diff.var(ddof=1))) if k > 1 else float('nan'))
+        return sum_and_se(self.elpd_lgo - other.elpd_lgo)
 
     def __str__(self):
         k = len(self.groups)
@@ -164,39 +162,21 @@ class _LgoStages(_Stages):
         import ctypes as C
         from ..device import _ptr
         L = self._lib
-        lib, chk = self.ctx._lib, L.check
-        out = self.ctx.empty((L.PLOO_NOUT, L.DIAG_BATCH))
+        out, head, tail = self.front(buf, L.DIAG_BATCH, nb, L.PLOO_ELL)
         lgo = self.ctx.empty((len(L.LGO_ROWS), L.DIAG_BATCH))
-        head = (self.ctx.handle, self.n, _ptr(buf), L.DIAG_BATCH, int(nb))
-        tail = (_ptr(self.work), self.work.numel())
-        chk(lib.bfhip_ploo_moments(*head, L.PLOO_ELL, None, _ptr(self.lb), _ptr(out), *tail))
-        chk(lib.bfhip_ploo_tail(*head, L.PLOO_ELL, None, _ptr(self.lb), _ptr(out), _ptr(self.keys), _ptr(self.idx), *tail))
-        chk(lib.bfhip_lgo_finish(*head, (C.c_double * int(nb))(*[float(v) for v in c]), (C.c_double * int(nb))(*[float(v) for v in dof]),
-                                 _ptr(self.lb), _ptr(self.keys), _ptr(self.idx), _ptr(out), _ptr(lgo), *tail))
+        L.check(self.ctx._lib.bfhip_lgo_finish(*head[:5], (C.c_double * int(nb))(*[float(v) for v in c]),
+                                               (C.c_double * int(nb))(*[float(v) for v in dof]), _ptr(self.lb), _ptr(self.keys),
+                                               _ptr(self.idx), _ptr(out), _ptr(lgo), *tail))   # head[:5]: handle, n, buf, ld, nb
         self.outs.append(out)
         self.lgo.append(lgo)
-        self.widths.append(int(nb))
 
     def group_result(self, groups, size):
-        import torch
         base = self.result(np.arange(len(groups)))   # the PSIS-LOO rows, in DataLOO's names
-        o = torch.stack(self.lgo).cpu().numpy()
-        o = np.concatenate([o[i][:, :nb] for i, nb in enumerate(self.widths)], axis=1)
+        o = self.collect(self.lgo, len(self._lib.LGO_ROWS))
         cols = dict(lpd=base.lpd, p_waic=base.p_waic, elpd_waic=base.elpd_waic, elpd_lgo=base.elpd_loo, p_lgo=base.p_loo, khat=base.khat,
                     sigma=base.sigma, ess_lgo=base.ess_loo, n_tail=base.n_tail)
         cols.update({name: o[i] for i, name in enumerate(self._lib.LGO_ROWS)})
         return DataLGO(groups, size, self.n, cols)
-
-
-def _base_log_weights(log_weights, like, n):
-    """``data_loo``'s normalised base log weights; where no row has any weight their logsumexp is -inf, and a row of -inf stays -inf
-    (not part of the sample) rather than turning into -inf - -inf."""
-    import torch
-    if log_weights is None:
-        return None
-    g = log_weights if isinstance(log_weights, torch.Tensor) else torch.as_tensor(np.asarray(log_weights))
-    g = g.detach().to(like.device).reshape(-1).to(torch.float64)
-    return torch.where(torch.isneginf(g), g, _normalise_device(g, like, n)).contiguous()
 
 
 def _device(q, dof, const, log_weights, groups):
@@ -211,7 +191,7 @@ def _device(q, dof, const, log_weights, groups):
     width = _lib.DIAG_BATCH
     with torch.cuda.device(q.device):
         ctx = get_context(q.device.index)
-        st = _LgoStages(ctx, n, _base_log_weights(log_weights, q, n))
+        st = _LgoStages(ctx, n, base_log_weights(log_weights, q, n, keep_neginf=True))
         buf = ctx.empty((n, width))
         qf = q.detach().reshape(n, k)
         ct = torch.as_tensor(const, dtype=torch.float64, device=q.device)
@@ -243,8 +223,7 @@ def grouped_loo(q, dof, const=None, log_weights=None):
     groups = [np.zeros(0, dtype=np.int64)] * k
     if getattr(q, 'is_cuda', False):
         return _device(q if q.ndim == 3 else q[None], dof, const, log_weights, groups)
-    host = lambda v: np.asarray(v.detach().cpu().numpy() if hasattr(v, 'detach') else v, dtype=np.float64)
-    return _host(host(q).reshape(n, k), dof, const, None if log_weights is None else host(log_weights), groups)
+    return _host(host_f64(q).reshape(n, k), dof, const, None if log_weights is None else host_f64(log_weights), groups)
 
 
 # ---- the pipeline's data ---------------------------------------------------------------------------------------------------------------
@@ -292,11 +271,7 @@ def group_whitening_of(prec=None, prec_diag=None, groups=None):
 
     groups : a sequence of K index sequences, each non-empty, sorted and unique, mutually disjoint, within [0, m); or an integer
         label array of length m, -1 for a point in no group (the groups are the labels in ascending order).  Anything else: ValueError."""
-    if (prec is None) == (prec_diag is None):
-        raise ValueError('give me exactly one of prec and prec_diag.')
-    p = np.asarray(prec, dtype=np.float64) if prec is not None else np.diag(np.asarray(prec_diag, dtype=np.float64).reshape(-1))
-    if p.ndim != 2 or p.shape[0] != p.shape[1] or not np.all(np.diag(p) > 0):
-        raise ValueError('the precision should be a square matrix with a positive diagonal.')
+    p = dense_precision(prec, prec_diag)
     if groups is None:
         raise ValueError('groups should be a sequence of index sequences or an integer label array.')
     from scipy.linalg import solve_triangular
@@ -323,32 +298,19 @@ def data_lgo(density, x, groups, log_weights=None):
     log_weights : one log importance weight per draw, e.g. ``psis(...).log_weights``."""
     import ctypes as C
     import torch
-    from .. import _lib, parallel
+    from .. import _lib
     from ..device import DevicePolyModel, polymodel_dense_from_poly, linear_dense, _ptr
-    if parallel.world()[1] > 1:
-        raise NotImplementedError('data_lgo covers one process: gather() the chains first.')
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise NotImplementedError('data_lgo reads a GPU tensor of draws: the package has no host evaluation of a PolyModel.')
-    if not (hasattr(density, 'surrogate') and hasattr(density, '_y')):
-        raise ValueError('density should be a Chi2PipelineDensity.')
+    check_one_process('data_lgo')
+    check_gpu_draws('data_lgo', x)
+    check_density(density)
     su = density.surrogate
-    if x.dim() == 2:
-        x = x[None]
-    d = int(su.input_size)
-    if x.dim() != 3 or int(x.shape[2]) != d:
-        raise ValueError('x should be (n_chain, n_draw, %d) or (n, %d).' % (d, d))
-    n_chain, n_draw = int(x.shape[0]), int(x.shape[1])
+    x = shaped_draws(x, su.input_size)
+    n_chain, n_draw, d = (int(v) for v in x.shape)
     n = n_chain * n_draw
-    if n < 1:
-        raise ValueError('x is empty.')
-    if n > 2**31 - 1:
-        raise NotImplementedError('more than 2^31 - 1 draws.')
     if d > _lib.MAX_DIM:
         raise NotImplementedError('more than %d inputs.' % _lib.MAX_DIM)
     a, const, sizes, colg = group_whitening_of(density._prec, density._pdiag, groups)
     gs = _parse_groups(groups, int(su.output_size))
-    if x.dtype not in (torch.float64, torch.float32) or (d > 1 and x.stride(2) != 1):
-        x = x.to(torch.float64).contiguous()
     width = _lib.DIAG_BATCH
     first = np.concatenate([[0], np.cumsum(sizes)])   # a group's first column
     y = np.asarray(density._y, dtype=np.float64).reshape(-1)
@@ -357,11 +319,8 @@ def data_lgo(density, x, groups, log_weights=None):
         # next use (DevicePolyModel.upload_if_needed)
         rm = DevicePolyModel.from_dense(linear_dense(polymodel_dense_from_poly(su.poly_spec()), -a, a @ y))
         ctx = rm.ctx
-        lo = diff = None
-        if su._input_scales is not None:
-            lo = ctx.tensor(np.ascontiguousarray(su._input_scales[:, 0]), torch.float64)
-            diff = ctx.tensor(np.ascontiguousarray(su._input_scales_diff), torch.float64)
-        st = _LgoStages(ctx, n, _base_log_weights(log_weights, x, n))
+        lo, diff = input_map(ctx, su)
+        st = _LgoStages(ctx, n, base_log_weights(log_weights, x, n, keep_neginf=True))
         zbuf = ctx.empty((n_chain, n_draw, width))
         acc = ctx.empty((n, width))
         for g0 in range(0, len(gs), width):

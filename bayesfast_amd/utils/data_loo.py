@@ -46,6 +46,8 @@ correlated neighbours) makes every point influential and pushes khat above 0.7 f
 answer; one process; ``data_loo`` reads device tensors only; n <= 2^31 - 1."""
 import numpy as np
 
+from ._pipeline_data import (PsisStages, base_log_weights, check_density, check_gpu_draws, check_one_process, dense_precision, host_f64,
+                             input_map, logsumexp_host, shaped_draws, sum_and_se)
 from .psis import _psis_host, tail_size
 
 __all__ = ['data_loo', 'pointwise_loo', 'DataLOO']
@@ -64,12 +66,11 @@ class DataLOO:
         for name in _POINT:
             setattr(self, name, np.asarray(cols[name], dtype=np.float64))
         self.n_tail = np.asarray(cols['n_tail'], dtype=np.int64)
-        k = len(self.outputs)
+        for name in _TOTAL:
+            total, se = sum_and_se(getattr(self, name))
+            setattr(self, name + '_total', total)
+            setattr(self, 'se_' + name, se)
         with np.errstate(all='ignore'):
-            for name in _TOTAL:
-                v = getattr(self, name)
-                setattr(self, name + '_total', float(v.sum()))
-                setattr(self, 'se_' + name, float(np.sqrt(k * v.var(ddof=1))) if k > 1 else float('nan'))
             self.n_khat_bad = int((self.khat > 0.7).sum())
 
     def compare(self, other):
@@ -77,10 +78,7 @@ class DataLOO:
         hold the same points."""
         if not isinstance(other, DataLOO) or not np.array_equal(self.outputs, other.outputs):
             raise ValueError('the two results should hold the same points.')
-        diff = self.elpd_loo - other.elpd_loo
-        k = diff.size
-        with np.errstate(all='ignore'):
-            return float(diff.sum()), (float(np.sqrt(k * diff.var(ddof=1))) if k > 1 else float('nan'))
+        return sum_and_se(self.elpd_loo - other.elpd_loo)
 
     def __str__(self):
         k = len(self.outputs)
@@ -102,11 +100,6 @@ class DataLOO:
 
 
 # ---- the host port ---------------------------------------------------------------------------------------------------------------------
-def _logsumexp(a):
-    top = a.max()
-    return top + np.log(np.exp(a - top).sum())
-
-
 def _host_column(ell, lb, z):
     """Every figure of one column: ell (n,), lb (n,) normalised base log weights or None, z (n,) or None."""
     n = ell.size
@@ -119,13 +112,13 @@ def _host_column(ell, lb, z):
         b = np.full(n, -np.log(n)) if lb is None else lb
         ek, bk = ell[keep], b[keep]
         w = np.exp(bk) if lb is not None else np.full(ek.size, 1. / n)
-        lpd = _logsumexp(bk + ek)
+        lpd = logsumexp_host(bk + ek)
         mean = (w * ek).sum()
         p_waic = (w * (ek - mean)**2).sum() / (1. - (w * w).sum())
         r = np.full(n, -np.inf)
         r[keep] = (bk if lb is not None else 0.) - ek
         v, khat, sigma, _, _, ess = _psis_host(r)
-        elpd_loo = _logsumexp(v[keep] + ek)
+        elpd_loo = logsumexp_host(v[keep] + ek)
         out.update(lpd=lpd, p_waic=p_waic, elpd_waic=lpd - p_waic, elpd_loo=elpd_loo, p_loo=lpd - elpd_loo, khat=khat, sigma=sigma, ess_loo=ess)
         if z is not None:
             from scipy.special import ndtr
@@ -140,7 +133,7 @@ def _normalise_host(log_weights, n):
     if g.size != n:
         raise ValueError('log_weights should hold one value per draw.')
     with np.errstate(all='ignore'):
-        return g - _logsumexp(g)
+        return g - logsumexp_host(g)
 
 
 def _host(ell, log_weights, z):
@@ -151,52 +144,23 @@ def _host(ell, log_weights, z):
 
 
 # ---- the device route ------------------------------------------------------------------------------------------------------------------
-def _normalise_device(log_weights, like, n):
-    import torch
-    if log_weights is None:
-        return None
-    g = log_weights if isinstance(log_weights, torch.Tensor) else torch.as_tensor(np.asarray(log_weights))
-    g = g.detach().to(like.device).reshape(-1).to(torch.float64)
-    if g.numel() != n:
-        raise ValueError('log_weights should hold one value per draw.')
-    return (g - torch.logsumexp(g, 0)).contiguous()
-
-
-class _Stages:
+class _Stages(PsisStages):
     """The three stages on one (n, 16) series buffer after another: ``run(buf, ld, nb, mode, c)`` queues a batch, ``result(outputs)``
     makes the one copy to the host."""
 
     def __init__(self, ctx, n, lb):
-        import torch
-        from .. import _lib
-        self.ctx, self.n, self.lb, self._lib = ctx, int(n), lb, _lib
-        m1 = tail_size(self.n) + 1
-        self.work = ctx.empty((int(ctx._lib.bfhip_ploo_work_bytes(self.n)),), dtype=torch.uint8)
-        self.keys = ctx.empty((_lib.DIAG_BATCH, m1), dtype=torch.int64)
-        self.idx = ctx.empty((_lib.DIAG_BATCH, m1), dtype=torch.int32)
-        self.outs, self.widths = [], []
+        super().__init__(ctx, n, lb)
+        self.outs = []
 
     def run(self, buf, ld, nb, mode, c=None):
         from ..device import _ptr
-        lib, h, chk = self.ctx._lib, self.ctx.handle, self._lib.check
-        out = self.ctx.empty((self._lib.PLOO_NOUT, self._lib.DIAG_BATCH))
-        head = (h, self.n, _ptr(buf), int(ld), int(nb), int(mode), _ptr(c), _ptr(self.lb))
-        tail = (_ptr(self.work), self.work.numel())
-        chk(lib.bfhip_ploo_moments(*head, _ptr(out), *tail))
-        chk(lib.bfhip_ploo_tail(*head, _ptr(out), _ptr(self.keys), _ptr(self.idx), *tail))
-        chk(lib.bfhip_ploo_finish(*head, _ptr(self.keys), _ptr(self.idx), _ptr(out), *tail))
+        out, head, tail = self.front(buf, ld, nb, mode, c)
+        self._lib.check(self.ctx._lib.bfhip_ploo_finish(*head, _ptr(self.keys), _ptr(self.idx), _ptr(out), *tail))
         self.outs.append(out)
-        self.widths.append(int(nb))
 
     def result(self, outputs):
-        import torch
-        rows = self._lib.PLOO_ROWS
-        if self.outs:
-            o = torch.stack(self.outs).cpu().numpy()   # the one copy to the host, after the last launch
-            o = np.concatenate([o[i][:, :nb] for i, nb in enumerate(self.widths)], axis=1)
-        else:
-            o = np.zeros((self._lib.PLOO_NOUT, 0))
-        raw = {name: o[i] for i, name in enumerate(rows)}
+        o = self.collect(self.outs, self._lib.PLOO_NOUT)
+        raw = {name: o[i] for i, name in enumerate(self._lib.PLOO_ROWS)}
         with np.errstate(all='ignore'):
             p_waic = raw['waic'] / (1. - raw['sw2'])
             cols = dict(lpd=raw['lpd'], p_waic=p_waic, elpd_waic=raw['lpd'] - p_waic, elpd_loo=raw['elpd_loo'],
@@ -218,7 +182,7 @@ def _device(ell, log_weights):
     batches = _device_batches(ell, n)
     with torch.cuda.device(ell.device):
         ctx = get_context(ell.device.index)
-        st = _Stages(ctx, n, _normalise_device(log_weights, ell, n))
+        st = _Stages(ctx, n, base_log_weights(log_weights, ell, n))
         buf = ctx.empty((n, _lib.DIAG_BATCH))
         for xb, kb, nb in batches:
             _lib.check(ctx._lib.bfhip_wstat_columns(ctx.handle, n_chain, n_draw, int(xb.stride(0)), int(xb.stride(1)), _ptr(xb),
@@ -246,19 +210,15 @@ def pointwise_loo(ell, log_weights=None, z=None):
         if z is not None:
             raise NotImplementedError('on the device pit comes from data_loo, which knows z.')
         return _device(ell if ell.ndim == 3 else ell[None], log_weights)
-    host = lambda v: np.asarray(v.detach().cpu().numpy() if hasattr(v, 'detach') else v, dtype=np.float64)
-    return _host(host(ell).reshape(n, k), None if log_weights is None else host(log_weights), None if z is None else host(z).reshape(n, k))
+    return _host(host_f64(ell).reshape(n, k), None if log_weights is None else host_f64(log_weights),
+                 None if z is None else host_f64(z).reshape(n, k))
 
 
 # ---- the pipeline's data ---------------------------------------------------------------------------------------------------------------
 def whitening_of(prec=None, prec_diag=None):
     """(W, c) of the conditional residuals: W = diag(P_ii)^(-1/2) P and c_i = log(P_ii / 2 pi) / 2."""
-    if (prec is None) == (prec_diag is None):
-        raise ValueError('give me exactly one of prec and prec_diag.')
-    p = np.asarray(prec, dtype=np.float64) if prec is not None else np.diag(np.asarray(prec_diag, dtype=np.float64).reshape(-1))
+    p = dense_precision(prec, prec_diag)
     dg = np.diag(p)
-    if p.ndim != 2 or p.shape[0] != p.shape[1] or not np.all(dg > 0):
-        raise ValueError('the precision should be a square matrix with a positive diagonal.')
     return p / np.sqrt(dg)[:, None], 0.5 * np.log(dg / (2. * np.pi))
 
 
@@ -270,41 +230,25 @@ def data_loo(density, x, log_weights=None, outputs=None):
     log_weights : one log importance weight per draw, e.g. ``psis(...).log_weights``.
     outputs : indices of the data points (sorted, unique), default all."""
     import torch
-    from .. import _lib, parallel
+    from .. import _lib
     from ..device import DevicePolyModel, polymodel_dense_from_poly, residual_dense
     from .predictive import output_plan
-    if parallel.world()[1] > 1:
-        raise NotImplementedError('data_loo covers one process: gather() the chains first.')
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise NotImplementedError('data_loo reads a GPU tensor of draws: the package has no host evaluation of a PolyModel.')
-    if not (hasattr(density, 'surrogate') and hasattr(density, '_y')):
-        raise ValueError('density should be a Chi2PipelineDensity.')
+    check_one_process('data_loo')
+    check_gpu_draws('data_loo', x)
+    check_density(density)
     su = density.surrogate
-    if x.dim() == 2:
-        x = x[None]
-    d, m = int(su.input_size), int(su.output_size)
-    if x.dim() != 3 or int(x.shape[2]) != d:
-        raise ValueError('x should be (n_chain, n_draw, %d) or (n, %d).' % (d, d))
+    x = shaped_draws(x, su.input_size)
     n_chain, n_draw = int(x.shape[0]), int(x.shape[1])
     n = n_chain * n_draw
-    if n < 1:
-        raise ValueError('x is empty.')
-    if n > 2**31 - 1:
-        raise NotImplementedError('more than 2^31 - 1 draws.')
-    idx, batches = output_plan(outputs, m, _lib.DIAG_BATCH)
-    if x.dtype not in (torch.float64, torch.float32) or (d > 1 and x.stride(2) != 1):
-        x = x.to(torch.float64).contiguous()
+    idx, batches = output_plan(outputs, int(su.output_size), _lib.DIAG_BATCH)
     w, c = whitening_of(density._prec, density._pdiag)
     with torch.cuda.device(x.device):
         # the residual model takes the context's one polymodel slot; the surrogate's own device model uploads itself again at
         # its next use (DevicePolyModel.upload_if_needed)
         rm = DevicePolyModel.from_dense(residual_dense(polymodel_dense_from_poly(su.poly_spec()), density._y, w))
         ctx = rm.ctx
-        lo = diff = None
-        if su._input_scales is not None:
-            lo = ctx.tensor(np.ascontiguousarray(su._input_scales[:, 0]), torch.float64)
-            diff = ctx.tensor(np.ascontiguousarray(su._input_scales_diff), torch.float64)
-        st = _Stages(ctx, n, _normalise_device(log_weights, x, n))
+        lo, diff = input_map(ctx, su)
+        st = _Stages(ctx, n, base_log_weights(log_weights, x, n))
         buf = ctx.empty((n_chain, n_draw, _lib.DIAG_BATCH))
         done = 0
         for calls in batches:

@@ -43,6 +43,8 @@ weights, the number of draws, the extremes (``ranges=None``), and ONE sum of the
 sum, on every rank.  The result is identical, bin for bin, to one process over all draws."""
 import numpy as np
 
+from ._pipeline_data import host_f64
+
 __all__ = ['marginals', 'marginals_sharded', 'Marginals']
 
 MAX_BINS, MAX_BINS2D = 1024, 128
@@ -478,9 +480,8 @@ def _make_passes(x, given, kind, params, d_all):
             x = x[..., torch.as_tensor(params, device=x.device)]
         g = None if given is None else torch.as_tensor(given, device=x.device).detach().reshape(-1).to(torch.float64)
         return _DevicePasses(x.detach() if x.ndim == 3 else x.detach()[None], g, kind)
-    host = lambda v: np.asarray(v.detach().cpu().numpy() if hasattr(v, 'detach') else v, dtype=np.float64)
-    xh = host(x).reshape(-1, x.shape[-1])
-    return _HostPasses(xh if whole else xh[:, params], None if given is None else host(given).reshape(-1), kind)
+    xh = host_f64(x).reshape(-1, x.shape[-1])
+    return _HostPasses(xh if whole else xh[:, params], None if given is None else host_f64(given).reshape(-1), kind)
 
 
 def marginals(x, log_weights=None, weights=None, bins=64, bins2d=64, ranges=None, params=None, pairs='all', probs=(0.68, 0.95)):

@@ -25,6 +25,7 @@ Limits: device tensors only (the package has no host evaluation of a ``PolyModel
 at most 128 inputs; the chi-square is the likelihood's, without the prior or the decay term."""
 import numpy as np
 
+from ._pipeline_data import check_gpu_draws, input_map, shaped_draws
 from .diagnostics import Summary
 
 __all__ = ['predictive', 'Predictive', 'output_plan', 'batch_width']
@@ -222,33 +223,19 @@ def predictive(model, x, log_weights=None, outputs=None, probs=(0.16, 0.5, 0.84)
     from .psis import weighted_summary
     if parallel.world()[1] > 1:
         raise NotImplementedError('predictive covers one process: gather the chains first.')
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise NotImplementedError('predictive reads a GPU tensor of draws: the package has no host evaluation of a PolyModel.')
+    check_gpu_draws('predictive', x)
     density = model if hasattr(model, 'surrogate') and hasattr(model, '_y') else None
     su = model.surrogate if density is not None else model
     if not hasattr(su, 'poly_spec') or not hasattr(su, 'device_model'):
         raise ValueError('model should be a PolyModel or a Chi2PipelineDensity.')
-    if x.dim() == 2:
-        x = x[None]
-    d, m = int(su.input_size), int(su.output_size)
-    if x.dim() != 3 or int(x.shape[2]) != d:
-        raise ValueError('x should be (n_chain, n_draw, %d) or (n, %d).' % (d, d))
-    n_chain, n_draw = int(x.shape[0]), int(x.shape[1])
+    x = shaped_draws(x, su.input_size)
+    n_chain, n_draw, m = int(x.shape[0]), int(x.shape[1]), int(su.output_size)
     n = n_chain * n_draw
-    if n < 1:
-        raise ValueError('x is empty.')
-    if n > 2**31 - 1:
-        raise NotImplementedError('more than 2^31 - 1 draws.')
-    if x.dtype not in (torch.float64, torch.float32) or (d > 1 and x.stride(2) != 1):
-        x = x.to(torch.float64).contiguous()
     with torch.cuda.device(x.device):
         dm = su.device_model()
         ctx = dm.ctx
         alpha = float(dm._desc.alpha) if dm._desc.use_bound else None   # (an all-linear model ignores its bound)
-        lo = diff = None
-        if density is not None and su._input_scales is not None:
-            lo = ctx.tensor(np.ascontiguousarray(su._input_scales[:, 0]), torch.float64)
-            diff = ctx.tensor(np.ascontiguousarray(su._input_scales_diff), torch.float64)
+        lo, diff = input_map(ctx, su) if density is not None else (None, None)
         w = _weights_of(log_weights, x[:, :, 0])
         idx_all, _ = output_plan(outputs, m, 1)
         width = batch_width(batch_bytes, n, max(1, idx_all.size))

@@ -44,6 +44,7 @@ whatever n_d is.  Every device reduction has a fixed order, so the same input gi
 a parameter lands in.  At most 2^31 - 1 values."""
 import numpy as np
 
+from ._pipeline_data import host_f64
 from .diagnostics import Summary, _check_probs, _device_batches, _lerp
 
 __all__ = ['psis', 'PSISResult', 'weighted_summary']
@@ -138,11 +139,10 @@ def psis(logp, logq=None):
         if logp.numel() < 1:
             raise ValueError('logp is empty.')
         return _psis_device(logp, logq)
-    host = lambda v: np.asarray(v.detach().cpu().numpy() if hasattr(v, 'detach') else v, dtype=np.float64)
-    lw = host(logp)
+    lw = host_f64(logp)
     shape = lw.shape
     if logq is not None:
-        lq = host(logq)
+        lq = host_f64(logq)
         if lq.size != lw.size:
             raise ValueError('logp and logq should have the same size.')
         with np.errstate(all='ignore'):
@@ -279,8 +279,7 @@ def weighted_summary(x, log_weights=None, weights=None, probs=(0.05, 0.5, 0.95))
         g = torch.as_tensor(given, device=x.device).detach().reshape(-1).to(torch.float64)
         w = (torch.exp(g - g.max()) if weights is None else g).contiguous()
         return _device_table(x if x.ndim == 3 else x[None], w, probs)
-    host = lambda v: np.asarray(v.detach().cpu().numpy() if hasattr(v, 'detach') else v, dtype=np.float64)
-    g = host(given).reshape(-1)
+    g = host_f64(given).reshape(-1)
     with np.errstate(all='ignore'):
         w = np.exp(g - g.max()) if weights is None else g
-    return _host_table(host(x).reshape(n, x.shape[-1]), w, probs)
+    return _host_table(host_f64(x).reshape(n, x.shape[-1]), w, probs)

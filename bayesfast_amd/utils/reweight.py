@@ -44,6 +44,8 @@ posterior sits; mcse_mean ignores the autocorrelation of a chain; one process; `
 n <= 2^31 - 1."""
 import numpy as np
 
+from ._pipeline_data import (PsisStages, base_log_weights, check_density, check_gpu_draws, check_one_process, host_f64, input_map,
+                             logsumexp_host, shaped_draws)
 from .psis import _psis_host, tail_size
 
 __all__ = ['reweight_moments', 'data_reweight', 'data_log_ratio', 'Reweighted']
@@ -109,11 +111,6 @@ def _finish(n, head, s1, s2, sums, mean_base, s2_base, sw2_base):
 
 
 # ---- the host port ---------------------------------------------------------------------------------------------------------------------
-def _logsumexp(a):
-    top = a.max()
-    return top + np.log(np.exp(a - top).sum())
-
-
 def _host(x, l, log_weights):
     """x (n, d), l (n, K) float64, log_weights (n,) or None"""
     n, d = x.shape
@@ -122,7 +119,7 @@ def _host(x, l, log_weights):
     with np.errstate(all='ignore'):
         lb = None
         if log_weights is not None:
-            lb = log_weights - _logsumexp(log_weights)
+            lb = log_weights - logsumexp_host(log_weights)
         keep = np.ones(n, dtype=bool) if lb is None else lb > -np.inf
         xk = x[keep]
         wb = np.exp(lb[keep]) if lb is not None else np.full(xk.shape[0], 1. / n)
@@ -159,7 +156,7 @@ def _host(x, l, log_weights):
 
 
 # ---- the device route ------------------------------------------------------------------------------------------------------------------
-class _Stages:
+class _Stages(PsisStages):
     """Base table and scenario batches on one set of draws x (n_chain, n_draw, d), a device tensor read in place: ``run(buf, nb)``
     queues the three stages on an (n, 16) series buffer that holds -l, ``result()`` makes the one copy to the host."""
 
@@ -167,15 +164,14 @@ class _Stages:
         import torch
         from .. import _lib
         from ..device import _ptr
-        from .data_loo import _normalise_device
         from .diagnostics import _device_batches
-        self.ctx, self._lib, self.x = ctx, _lib, x
+        self.x = x
         self.n_chain, self.n_draw, self.d = (int(v) for v in x.shape)
-        n = self.n = self.n_chain * self.n_draw
+        n = self.n_chain * self.n_draw
         lib, h, width = ctx._lib, ctx.handle, _lib.DIAG_BATCH
-        self.lb = _normalise_device(log_weights, x, n)
+        lb = base_log_weights(log_weights, x, n)
         # the base table: bfhip_wstat_moments on batches of 16 parameters under the base weights
-        w = torch.exp(self.lb) if self.lb is not None else torch.full((n,), 1. / n, dtype=torch.float64, device=x.device)
+        w = torch.exp(lb) if lb is not None else torch.full((n,), 1. / n, dtype=torch.float64, device=x.device)
         work = ctx.empty((_lib.WSTAT_WORK,))
         self.wsum = ctx.empty((4,))
         _lib.check(lib.bfhip_wstat_moments(h, n, None, _ptr(w), _ptr(self.wsum), None, _ptr(work)))
@@ -189,37 +185,26 @@ class _Stages:
             parts.append(out[:, :nb])
         self.base = torch.cat(parts, dim=1)            # rows mean, sum w (x - mean)^2, ...
         self.centre = self.base[0].contiguous()
-        m1 = tail_size(n) + 1
-        self.work = ctx.empty((int(lib.bfhip_ploo_work_bytes(n)),), dtype=torch.uint8)
+        super().__init__(ctx, n, lb)
         self.rw_work = ctx.empty((int(lib.bfhip_rw_work_bytes(n, self.d)),), dtype=torch.uint8)
-        self.keys = ctx.empty((width, m1), dtype=torch.int64)
-        self.idx = ctx.empty((width, m1), dtype=torch.int32)
-        self.outs, self.widths = [], []
+        self.outs = []
 
     def run(self, buf, nb):
         import torch
         from ..device import _ptr
         _lib, x = self._lib, self.x
-        lib, chk = self.ctx._lib, _lib.check
-        out = self.ctx.empty((_lib.PLOO_NOUT, _lib.DIAG_BATCH))
+        out, head, tail = self.front(buf, _lib.DIAG_BATCH, nb, _lib.PLOO_ELL)
         rw = self.ctx.empty((_lib.RW_SUMS + 2 * (1 + 2 * self.d), _lib.DIAG_BATCH))
-        head = (self.ctx.handle, self.n, _ptr(buf), _lib.DIAG_BATCH, int(nb), _lib.PLOO_ELL, None, _ptr(self.lb))
-        tail = (_ptr(self.work), self.work.numel())
         ldr = int(x.stride(1)) if self.n_draw > 1 else self.d
-        chk(lib.bfhip_ploo_moments(*head, _ptr(out), *tail))
-        chk(lib.bfhip_ploo_tail(*head, _ptr(out), _ptr(self.keys), _ptr(self.idx), *tail))
-        chk(lib.bfhip_rw_finish(*head, _ptr(self.keys), _ptr(self.idx), _ptr(out), *tail, self.n_chain, self.n_draw, int(x.stride(0)), ldr,
-                                _ptr(x), int(x.dtype == torch.float32), 0, self.d, _ptr(self.centre), _ptr(rw), _ptr(self.rw_work),
-                                self.rw_work.numel()))
+        _lib.check(self.ctx._lib.bfhip_rw_finish(*head, _ptr(self.keys), _ptr(self.idx), _ptr(out), *tail, self.n_chain, self.n_draw,
+                                                 int(x.stride(0)), ldr, _ptr(x), int(x.dtype == torch.float32), 0, self.d, _ptr(self.centre),
+                                                 _ptr(rw), _ptr(self.rw_work), self.rw_work.numel()))
         self.outs.append(rw)
-        self.widths.append(int(nb))
 
     def result(self):
-        import torch
         d, r0 = self.d, self._lib.RW_SUMS
         base, ws = self.base.cpu().numpy(), self.wsum.cpu().numpy()
-        o = torch.stack(self.outs).cpu().numpy()   # the one copy of the scenarios to the host, after the last launch
-        o = np.concatenate([o[i][:, :nb] for i, nb in enumerate(self.widths)], axis=1)
+        o = self.collect(self.outs, r0 + 2 * (1 + 2 * d))   # the one copy of the scenarios to the host
         raw = {name: o[i] for i, name in enumerate(self._lib.RW_ROWS)}
         head = {name: raw[name] for name in ('khat', 'sigma', 'ess')}
         head['log_evidence_ratio'] = raw['log_evidence_ratio'] + (0. if self.lb is not None else -np.log(self.n))
@@ -229,13 +214,6 @@ class _Stages:
         return _finish(self.n, head, o[r0], o[r0 + nf], sums, base[0], base[1], float(ws[1]))
 
 
-def _draws_for_device(x):
-    import torch
-    if x.dtype not in (torch.float64, torch.float32) or (x.shape[2] > 1 and x.stride(2) != 1):
-        x = x.to(torch.float64).contiguous()
-    return x
-
-
 def _device(x, l, log_weights):
     """x (n_chain, n_draw, d) and l (n_chain, n_draw, K) device tensors"""
     import torch
@@ -243,13 +221,12 @@ def _device(x, l, log_weights):
     from ..device import get_context
     n_chain, n_draw, big_k = (int(v) for v in l.shape)
     n = n_chain * n_draw
-    if n > 2**31 - 1:
-        raise NotImplementedError('more than 2^31 - 1 draws.')
+    x = shaped_draws(x, x.shape[2])   # (refuses n > 2^31 - 1 before anything is allocated)
     if int(x.shape[2]) > _lib.MAX_DIM:
         raise NotImplementedError('more than %d parameters.' % _lib.MAX_DIM)
     with torch.cuda.device(x.device):
         ctx = get_context(x.device.index)
-        st = _Stages(ctx, _draws_for_device(x.detach()), log_weights)
+        st = _Stages(ctx, x, log_weights)
         buf = ctx.empty((n, _lib.DIAG_BATCH))
         lf = l.detach().reshape(n, big_k)
         for k0 in range(0, big_k, _lib.DIAG_BATCH):
@@ -278,8 +255,8 @@ def reweight_moments(x, log_ratio, log_weights=None):
         import torch
         l = torch.as_tensor(log_ratio, device=x.device)
         return _device(x if x.ndim == 3 else x[None], l if l.ndim == 3 else l[None], log_weights)
-    host = lambda v: np.asarray(v.detach().cpu().numpy() if hasattr(v, 'detach') else v, dtype=np.float64)
-    return _host(host(x).reshape(n, d), host(log_ratio).reshape(n, -1), None if log_weights is None else host(log_weights).reshape(-1))
+    return _host(host_f64(x).reshape(n, d), host_f64(log_ratio).reshape(n, -1),
+                 None if log_weights is None else host_f64(log_weights).reshape(-1))
 
 
 # ---- the pipeline's data ---------------------------------------------------------------------------------------------------------------
@@ -298,29 +275,16 @@ def ratio_coefficients(y, y_new, prec=None, prec_diag=None):
 
 
 def _prepare(who, density, x, y_new):
-    """The checks of ``data_loo``, in its words -> (x (n_chain, n_draw, d), dense arrays of the surrogate, A, b)."""
-    import torch
-    from .. import parallel
+    """The checks of ``data_loo``, in its words, the density before the draws -> (x (n_chain, n_draw, d), dense arrays of the
+    surrogate, A, b)."""
     from ..device import polymodel_dense_from_poly
-    if parallel.world()[1] > 1:
-        raise NotImplementedError('%s covers one process: gather() the chains first.' % who)
-    if not (hasattr(density, 'surrogate') and hasattr(density, '_y')):
-        raise ValueError('density should be a Chi2PipelineDensity.')
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise NotImplementedError('%s reads a GPU tensor of draws: the package has no host evaluation of a PolyModel.' % who)
+    check_one_process(who)
+    check_density(density)
+    check_gpu_draws(who, x)
     su = density.surrogate
-    if x.dim() == 2:
-        x = x[None]
-    d = int(su.input_size)
-    if x.dim() != 3 or int(x.shape[2]) != d:
-        raise ValueError('x should be (n_chain, n_draw, %d) or (n, %d).' % (d, d))
-    n = int(x.shape[0]) * int(x.shape[1])
-    if n < 1:
-        raise ValueError('x is empty.')
-    if n > 2**31 - 1:
-        raise NotImplementedError('more than 2^31 - 1 draws.')
+    x = shaped_draws(x, su.input_size)
     a, b = ratio_coefficients(density._y, y_new, density._prec, density._pdiag)
-    return _draws_for_device(x.detach()), polymodel_dense_from_poly(su.poly_spec()), a, b
+    return x, polymodel_dense_from_poly(su.poly_spec()), a, b
 
 
 def _chunks(dense, big_k, chunk_bytes, width):
@@ -333,17 +297,14 @@ def _chunks(dense, big_k, chunk_bytes, width):
 
 def _ratio_columns(density, x, dense, a, b, chunk_bytes, width, sink):
     """Every scenario's column of A f + b in batches of at most ``width``: ``sink(rm, k0_global, k0_in_model, nb, lo, diff)`` evaluates."""
-    import torch
     from ..device import DevicePolyModel, linear_dense
-    su = density.surrogate
     lo = diff = None
     for c0, ck in _chunks(dense, a.shape[0], chunk_bytes, width):
         # the ratio model takes the context's one polymodel slot; the surrogate's own device model uploads itself again at its next
         # use (DevicePolyModel.upload_if_needed)
         rm = DevicePolyModel.from_dense(linear_dense(dense, a[c0:c0 + ck], b[c0:c0 + ck]))
-        if su._input_scales is not None and lo is None:
-            lo = rm.ctx.tensor(np.ascontiguousarray(su._input_scales[:, 0]), torch.float64)
-            diff = rm.ctx.tensor(np.ascontiguousarray(su._input_scales_diff), torch.float64)
+        if c0 == 0:
+            lo, diff = input_map(rm.ctx, density.surrogate)
         for k0 in range(0, ck, width):
             sink(rm, c0 + k0, k0, min(width, ck - k0), lo, diff)
 
