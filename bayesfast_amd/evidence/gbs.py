@@ -65,9 +65,7 @@ def _device_samples(trace):
     t = trace.device('samples_original')
     if not isinstance(t, torch.Tensor) or t.dim() != 3:
         return None
-    if trace.n_warmup >= trace.i_iter - 1:
-        raise ValueError('since_iter is too large. Nothing to return.')
-    return t[:, trace.n_warmup:]
+    return t[:, trace._start():]
 
 
 def _device_density(logp):

@@ -16,7 +16,9 @@ reference's classes (the bases are taken from the imported package at call time;
 * ``TraceTuple``       subclass of ``bayesfast.samplers.TraceTuple`` over the device-resident result: ``get``, ``samples``,
                        ``logp`` ... read the device arrays; iterating it yields real ``NTrace`` / ``HTrace`` objects (one per
                        chain, built lazily) whose ``step_size`` is a ``DualAverageAdaptation`` and whose ``metric`` is a
-                       ``QuadMetric*`` carrying the adapted state, so ``_get_step_size`` / ``_get_metric`` accept them.
+                       ``QuadMetric*`` carrying the adapted state, so ``_get_step_size`` / ``_get_metric`` accept them.  Every
+                       analysis reader that ``bayesfast_amd.TraceTuple.READERS`` names (``rhat``, ``summary``, ``marginals``,
+                       ``kde``, ``modes`` ...) is forwarded to the device result, from that one list.
 * ``sample``           the signature of ``bayesfast.core.sample.sample``: takes the reference's ``Density`` (read by duck
                        typing, ``adapters.py``) and the reference's ``NTrace`` / ``HTrace`` / dict / a ``TraceTuple`` returned
                        earlier (continue the chains), runs all chains in fused device launches.
@@ -273,33 +275,8 @@ def reference_classes(bayesfast=None):
 
         __call__ = get
 
-        # ---- the convergence checks of the device result, read where the sampler left it (the reference's TraceTuple has none) ----
-        def integrated_time(self, *args, **kwargs):
-            return self._inner.integrated_time(*args, **kwargs)
-
-        def rhat(self, *args, **kwargs):
-            return self._inner.rhat(*args, **kwargs)
-
-        def ess(self, *args, **kwargs):
-            return self._inner.ess(*args, **kwargs)
-
-        def summary(self, *args, **kwargs):
-            return self._inner.summary(*args, **kwargs)
-
-        def predictive(self, *args, **kwargs):
-            return self._inner.predictive(*args, **kwargs)
-
-        def data_loo(self, *args, **kwargs):
-            return self._inner.data_loo(*args, **kwargs)
-
-        def data_lgo(self, *args, **kwargs):
-            return self._inner.data_lgo(*args, **kwargs)
-
-        def data_reweight(self, *args, **kwargs):
-            return self._inner.data_reweight(*args, **kwargs)
-
-        def profile(self, *args, **kwargs):
-            return self._inner.profile(*args, **kwargs)
+        # ---- the analysis readers of the device result (``bayesfast_amd.TraceTuple.READERS``; the reference's TraceTuple has none)
+        # are attached below the class ----
 
         # ---- per-chain traces of the reference's own classes, for _get_step_size / _get_metric / users ----
         @property
@@ -353,6 +330,18 @@ def reference_classes(bayesfast=None):
                 cls = _HStats if self._sampler == 'HMC' else _NStats
                 t._stats = cls()._fill(inner._stats[i], inner.n_warmup)
             return t
+
+    def _forward(name):
+        def reader(self, *args, **kwargs):
+            # (a seam TraceTuple among the arguments -- parameter_shift's ``other`` -- stands for the result it wraps)
+            args = [a._inner if isinstance(a, TraceTuple) else a for a in args]
+            kwargs = {k: a._inner if isinstance(a, TraceTuple) else a for k, a in kwargs.items()}
+            return getattr(self._inner, name)(*args, **kwargs)
+        reader.__name__, reader.__doc__ = name, getattr(_our_st.TraceTuple, name).__doc__
+        return reader
+
+    for name in _our_st.TraceTuple.READERS:
+        setattr(TraceTuple, name, _forward(name))
 
     ref_laplace = bf.utils.laplace
 

@@ -256,6 +256,9 @@ class TraceTuple:
     ``bayesfast_amd.core.refit.select_fit_points``, and the warm-start helpers reduce over the ranks on the device."""
 
     _FIELDS = ('samples', 'stats', 'samples_original', 'logp_original')
+    # the analysis readers: what the reference's TraceTuple does not have (``integrate.py`` forwards exactly these)
+    READERS = ('integrated_time', 'rhat', 'ess', 'summary', 'weighted_summary', 'predictive', 'data_loo', 'data_lgo', 'data_reweight',
+               'profile', 'marginals', 'kde', 'modes', 'parameter_shift')
 
     def __init__(self, trace, samples, stats, samples_original, logp_original, chains=None, stats_t=None):
         self._trace = trace
@@ -371,14 +374,46 @@ class TraceTuple:
             return self._array('stats_t')[:, :, ('u', 'weight').index(name)]
         return self._stats[:, :, self._stat_items.index(name)]
 
-    def get(self, since_iter=None, include_warmup=False, original_space=True, return_type='samples', flatten=True):
-        if return_type == 'all':
-            return [self.get(since_iter, include_warmup, original_space, r, flatten) for r in ('samples', 'logp')]
+    # ---- the draw selection: every reader below goes through these ----
+    def _start(self, since_iter=None, include_warmup=False):
+        """The first iteration that ``since_iter`` / ``include_warmup`` select."""
         if since_iter is None:
             since_iter = 0 if include_warmup else self.n_warmup
         since_iter = int(since_iter)
         if since_iter >= self.i_iter - 1:
             raise ValueError('since_iter is too large. Nothing to return.')
+        return since_iter
+
+    def _view(self, since_iter, include_warmup, original_space=True, return_type='samples'):
+        """This rank's chains of what ``get(..., flatten=False)`` selects, as a view of the parts as stored
+        (n_chain_local, n_t, n_d), unmaterialised; ``'logp'``: n_d = 1."""
+        since_iter = self._start(since_iter, include_warmup)
+        if return_type == 'samples':
+            return self._parts['samples_original' if original_space else 'samples'][:, since_iter:]
+        if return_type == 'logp':
+            if original_space:
+                return self._parts['logp_original'][:, since_iter:, None]
+            return self._parts['stats'][:, since_iter:, 0:1]
+        raise ValueError('invalid value for return_type.')
+
+    @staticmethod
+    def _single_process(why):
+        """The refusal of the readers that need the draws of ALL chains where this object holds one rank's."""
+        from .. import parallel
+        if parallel.world()[1] > 1:
+            raise NotImplementedError(why)
+
+    def _diag_input(self, since_iter, include_warmup, original_space, return_type):
+        """``_view`` for the single-process readers."""
+        self._single_process('rhat, ess and summary rank every value among the draws of ALL chains, and this TraceTuple '
+                             'holds one rank\'s: gather the chains and use the host port, '
+                             'utils.diagnostics.summary(tt.gather().get(flatten=False)).')
+        return self._view(since_iter, include_warmup, original_space, return_type)
+
+    def get(self, since_iter=None, include_warmup=False, original_space=True, return_type='samples', flatten=True):
+        if return_type == 'all':
+            return [self.get(since_iter, include_warmup, original_space, r, flatten) for r in ('samples', 'logp')]
+        since_iter = self._start(since_iter, include_warmup)
         if return_type == 'samples':
             s = (self._samples_original if original_space else self._samples)[:, since_iter:]
             return s.reshape((-1, self.input_size)) if flatten else s
@@ -398,47 +433,15 @@ class TraceTuple:
         rank; every rank gets the same tau and only lag sums cross between ranks (no ``gather()``)."""
         from .. import parallel
         from ..utils import acor
-        if since_iter is None:
-            since_iter = 0 if include_warmup else self.n_warmup
-        since_iter = int(since_iter)
-        if since_iter >= self.i_iter - 1:
-            raise ValueError('since_iter is too large. Nothing to return.')
-        if return_type == 'samples':
-            x = self._parts['samples_original' if original_space else 'samples'][:, since_iter:]
-        elif return_type == 'logp':
-            if original_space:
-                x = self._parts['logp_original'][:, since_iter:, None]
-            else:
-                x = self._parts['stats'][:, since_iter:, 0:1]
-                x = x.contiguous() if hasattr(x, 'contiguous') else np.ascontiguousarray(x)
-        else:
-            raise ValueError('invalid value for return_type.')
+        x = self._view(since_iter, include_warmup, original_space, return_type)
+        if return_type == 'logp' and not original_space:     # a column of the statistics table
+            x = x.contiguous() if hasattr(x, 'contiguous') else np.ascontiguousarray(x)
         if parallel.world()[1] == 1 and not getattr(x, 'is_cuda', False):
             return acor.integrated_time(np.asarray(x), c, tol, quiet)      # host parts: the host port
         if not hasattr(x, 'is_cuda'):
             import torch
             x = torch.as_tensor(x)
         return acor.integrated_time_sharded(x, self.n_chain, c, tol, quiet)
-
-    def _diag_input(self, since_iter, include_warmup, original_space, return_type):
-        """What ``get(..., flatten=False)`` selects, as a view of this rank's parts (n_chain, n_t, n_d), unmaterialised."""
-        from .. import parallel
-        if parallel.world()[1] > 1:
-            raise NotImplementedError('rhat, ess and summary rank every value among the draws of ALL chains, and this TraceTuple '
-                                      'holds one rank\'s: gather the chains and use the host port, '
-                                      'utils.diagnostics.summary(tt.gather().get(flatten=False)).')
-        if since_iter is None:
-            since_iter = 0 if include_warmup else self.n_warmup
-        since_iter = int(since_iter)
-        if since_iter >= self.i_iter - 1:
-            raise ValueError('since_iter is too large. Nothing to return.')
-        if return_type == 'samples':
-            return self._parts['samples_original' if original_space else 'samples'][:, since_iter:]
-        if return_type == 'logp':
-            if original_space:
-                return self._parts['logp_original'][:, since_iter:, None]
-            return self._parts['stats'][:, since_iter:, 0:1]
-        raise ValueError('invalid value for return_type.')
 
     def rhat(self, since_iter=None, include_warmup=False, original_space=True, return_type='samples', method='rank'):
         """R-hat (n_d,) of the chains (``bayesfast_amd.utils.rhat``) over what ``get(since_iter, include_warmup, original_space,
@@ -466,13 +469,11 @@ class TraceTuple:
         ``log_weights`` (``bayesfast_amd.utils.weighted_summary``; one log weight per selected draw, shaped (n_chain, n_t) or flat
         in that order, e.g. ``psis(...).log_weights``), read where ``sample()`` left the chains; selection as ``summary``.  Single
         process only: with more than one rank it raises ``NotImplementedError``."""
-        from .. import parallel
         from ..utils.psis import weighted_summary
-        if parallel.world()[1] > 1:
-            raise NotImplementedError('the weights are normalised over the draws of ALL chains, and this TraceTuple holds one rank\'s: '
-                                      'gather the chains and use the host port, '
-                                      'utils.weighted_summary(tt.gather().get(flatten=False), log_weights).')
-        return weighted_summary(self._diag_input(since_iter, include_warmup, original_space, return_type), log_weights=log_weights,
+        self._single_process('the weights are normalised over the draws of ALL chains, and this TraceTuple holds one rank\'s: '
+                             'gather the chains and use the host port, '
+                             'utils.weighted_summary(tt.gather().get(flatten=False), log_weights).')
+        return weighted_summary(self._view(since_iter, include_warmup, original_space, return_type), log_weights=log_weights,
                                 probs=probs)
 
     def predictive(self, density, log_weights=None, since_iter=None, include_warmup=False, **kw):
@@ -513,37 +514,16 @@ class TraceTuple:
         from ..utils.profile import profile_from_draws
         return profile_from_draws(self._diag_input(since_iter, include_warmup, False, 'samples'), density, **kw)
 
-    def _local_samples(self, since_iter, include_warmup, original_space):
-        """This rank's chains of what ``get(..., flatten=False)`` selects, as a view of the parts (n_chain_local, n_t, n_d),
-        unmaterialised; unlike ``_diag_input`` with any number of ranks: for the statistics that are collectives."""
-        if since_iter is None:
-            since_iter = 0 if include_warmup else self.n_warmup
-        since_iter = int(since_iter)
-        if since_iter >= self.i_iter - 1:
-            raise ValueError('since_iter is too large. Nothing to return.')
-        return self._parts['samples_original' if original_space else 'samples'][:, since_iter:]
-
     def marginals(self, log_weights=None, since_iter=None, include_warmup=False, original_space=True, **options):
-        """The marginal posterior histograms and credible levels (``bayesfast_amd.utils.marginals``: a ``Marginals``) of the draws
+        """The marginal posterior histograms and credible levels (``utils.marginals.marginals_of_shard``: a ``Marginals``) of the draws
         that ``get(since_iter, include_warmup, original_space, flatten=False)`` selects, read where ``sample()`` left them;
         ``options`` are ``bins``, ``bins2d``, ``ranges``, ``params``, ``pairs`` and ``probs``.  ``log_weights``, if given, holds one
         log weight per selected draw of THIS rank, shaped (n_chain_local, n_t) or flat in that order.  Under ``torch.distributed``
         with more than one rank a collective, to be called by every rank: every rank gets the same result, identical bin for bin
         to one process over all chains, and only the weights' maximum, the draw count, the extremes and the int64 bins cross
         between ranks (no ``gather()``)."""
-        from ..utils.marginals import _weights_of, _check_options, _make_passes, marginals_sharded
-        x = self._local_samples(since_iter, include_warmup, original_space)
-        unknown = set(options) - {'bins', 'bins2d', 'ranges', 'params', 'pairs', 'probs'}
-        if unknown:
-            raise TypeError('unexpected options: %s.' % ', '.join(sorted(unknown)))
-        opt = dict(bins=64, bins2d=64, ranges=None, params=None, pairs='all', probs=(0.68, 0.95))
-        opt.update(options)
-        d_all = int(x.shape[-1])
-        given, kind = _weights_of(tuple(x.shape), log_weights, None)
-        checked = _check_options(d_all, **opt)
-        if getattr(x, 'is_cuda', False) and len(checked[4]) and len(checked[3]) > _lib.MARG_MAX_LD:
-            raise NotImplementedError('pairs of more than %d parameters on the device route.' % _lib.MARG_MAX_LD)
-        return marginals_sharded(_make_passes(x, given, kind, checked[3], d_all), *checked)
+        from ..utils.marginals import marginals_of_shard
+        return marginals_of_shard(self._view(since_iter, include_warmup, original_space), log_weights=log_weights, **options)
 
     def kde(self, log_weights=None, since_iter=None, include_warmup=False, original_space=True, params=None, **kw):
         """The kernel density estimate (``bayesfast_amd.utils.kde``) of the draws that ``get(since_iter, include_warmup,
@@ -551,62 +531,24 @@ class TraceTuple:
         ``log_weights``, if given, holds one log weight per selected draw, shaped (n_chain, n_t) or flat in that order; ``params``
         selects parameters by index; ``kw`` are ``bw_method`` and ``bw_factor``.  Single process only: with more than one rank it
         raises ``NotImplementedError``."""
-        from .. import parallel
-        from ..utils.kde import kde
-        if parallel.world()[1] > 1:
-            raise NotImplementedError('the estimate is built from the draws of ALL chains, and this TraceTuple holds one rank\'s: '
-                                      'gather the chains and use the host port, utils.kde(tt.gather().get(flatten=True)).')
-        x = self._diag_input(since_iter, include_warmup, original_space, 'samples')
-        x = x.reshape((-1, x.shape[-1]))
-        if params is not None:
-            x = x[:, [int(p) for p in params]]
-        if log_weights is not None:
-            log_weights = log_weights.reshape(-1)
+        from ..utils.kde import kde, flat_draws
+        self._single_process('the estimate is built from the draws of ALL chains, and this TraceTuple holds one rank\'s: '
+                             'gather the chains and use the host port, utils.kde(tt.gather().get(flatten=True)).')
+        x, log_weights = flat_draws(self._view(since_iter, include_warmup, original_space), log_weights, params)
         return kde(x, log_weights=log_weights, **kw)
 
     def modes(self, log_weights=None, since_iter=None, include_warmup=False, original_space=True, per_chain=4, **kw):
-        """The modes (``bayesfast_amd.utils.modes``: a ``Modes``) of the kernel density estimate of the draws that ``get(since_iter,
+        """The modes (``utils.modes.modes_by_chain``: a ``Modes``) of the kernel density estimate of the draws that ``get(since_iter,
         include_warmup, original_space, flatten=True)`` selects, and which chains sit in which.  The mean-shift seeds are
         ``per_chain`` evenly spaced draws of every chain; with ``log_weights`` ((n_chain, n_t) or flat in that order) a chain's
         ``per_chain`` seeds are resampled within the chain in proportion to the weights.  ``kw`` are ``params``, ``bw_method``,
         ``bw_factor``, ``tol``, ``max_iter``, ``merge_tol``, ``min_share`` and ``seed``.  The result also has ``chain_mode``
         (n_chain,), the majority label of the chain's seeds (ties to the lower label), and ``chain_split`` (n_chain,), whether its
         seeds disagree.  Single process only: with more than one rank it raises ``NotImplementedError``."""
-        from .. import parallel
-        from ..utils.kde import kde, _host
-        from ..utils.modes import modes_from_seeds, systematic_rows
-        if parallel.world()[1] > 1:
-            raise NotImplementedError('the modes are those of the draws of ALL chains, and this TraceTuple holds one rank\'s: '
-                                      'gather the chains and use the host port, utils.modes(tt.gather().get(flatten=True)).')
-        x = self._diag_input(since_iter, include_warmup, original_space, 'samples')
-        n_chain, n_t, per_chain = int(x.shape[0]), int(x.shape[1]), int(per_chain)
-        if per_chain < 1:
-            raise ValueError('per_chain should be at least 1.')
-        x = x.reshape((-1, x.shape[-1]))
-        params, seed = kw.pop('params', None), kw.pop('seed', 0)
-        if params is not None:
-            x = x[:, [int(p) for p in params]]
-        if log_weights is not None:
-            log_weights = log_weights.reshape(-1)
-        est = kde(x, log_weights=log_weights, bw_method=kw.pop('bw_method', None), bw_factor=kw.pop('bw_factor', None))
-        if log_weights is None:
-            t = ((np.arange(per_chain) + 0.5) * n_t / per_chain).astype(np.int64)
-            rows = (np.arange(n_chain)[:, None] * n_t + t[None, :]).reshape(-1)
-        else:
-            rng = np.random.default_rng(seed)
-            w = _host(est.weights).reshape(n_chain, n_t)
-            rows = np.concatenate([c * n_t + (systematic_rows(w[c], per_chain, rng) if w[c].sum() > 0. else np.zeros(per_chain, np.int64))
-                                   for c in range(n_chain)])
-        out = modes_from_seeds(est, rows, **kw)
-        label = out.label.reshape(n_chain, per_chain)
-        out.chain_mode = np.full(n_chain, -1, dtype=np.int64)
-        out.chain_split = np.zeros(n_chain, dtype=bool)
-        for c in range(n_chain):
-            got = label[c][label[c] >= 0]
-            if got.size:
-                out.chain_mode[c] = int(np.argmax(np.bincount(got)))     # the first of equal counts: the lower label
-                out.chain_split[c] = bool(np.any(got != got[0]))
-        return out
+        from ..utils.modes import modes_by_chain
+        self._single_process('the modes are those of the draws of ALL chains, and this TraceTuple holds one rank\'s: '
+                             'gather the chains and use the host port, utils.modes(tt.gather().get(flatten=True)).')
+        return modes_by_chain(self._view(since_iter, include_warmup, original_space), log_weights, per_chain, **kw)
 
     def parameter_shift(self, other, log_weights=None, log_weights_other=None, since_iter=None, include_warmup=False,
                         original_space=True, **kw):
@@ -615,15 +557,13 @@ class TraceTuple:
         ``TraceTuple`` (the same selection is applied to it) or a tensor or array of draws (n, d).  ``kw`` are ``params``,
         ``n_pairs``, ``bw_method``, ``bw_factor``, ``loo`` and ``seed``.  The two chains are assumed independent.  Single
         process only: with more than one rank it raises ``NotImplementedError``."""
-        from .. import parallel
         from ..utils.shift import parameter_shift
-        if parallel.world()[1] > 1:
-            raise NotImplementedError('the difference sample pairs the draws of ALL chains, and this TraceTuple holds one rank\'s: '
-                                      'gather the chains and use the host port, '
-                                      'utils.parameter_shift(tt.gather().get(flatten=True), other.gather().get(flatten=True)).')
-        x = self._diag_input(since_iter, include_warmup, original_space, 'samples')
+        self._single_process('the difference sample pairs the draws of ALL chains, and this TraceTuple holds one rank\'s: '
+                             'gather the chains and use the host port, '
+                             'utils.parameter_shift(tt.gather().get(flatten=True), other.gather().get(flatten=True)).')
+        x = self._view(since_iter, include_warmup, original_space)
         if isinstance(other, TraceTuple):
-            other = other._diag_input(since_iter, include_warmup, original_space, 'samples')
+            other = other._view(since_iter, include_warmup, original_space)
         return parameter_shift(x, other, log_weights_a=log_weights, log_weights_b=log_weights_other, **kw)
 
     def __getitem__(self, key):

@@ -55,6 +55,17 @@ def _host(a):
     return np.asarray(a.detach().cpu().numpy() if hasattr(a, 'detach') else a)
 
 
+def flat_draws(x, log_weights=None, params=None):
+    """Per-chain draws ``x`` (n_chain, n_t, d), host or device, and their log weights ((n_chain, n_t), flat in that order, or None) as
+    the rows (n_chain n_t, d) of the parameters ``params`` (indices; None: all) and the flat weights an estimate is built from."""
+    x = x.reshape((-1, x.shape[-1]))
+    if params is not None:
+        x = x[:, [int(p) for p in params]]
+    if log_weights is not None:
+        log_weights = log_weights.reshape(-1)
+    return x, log_weights
+
+
 # ---- the pairwise sum: out[i] = log sum_j exp(logw[j] - |zq_i - z_j|^2 / 2) ---------------------------------------------------------
 def _logsum_host(z, logw, zq, exclude_self=False):
     n, m = z.shape[0], zq.shape[0]

@@ -41,11 +41,13 @@ everything; with ``log_weights=`` the device's exp and NumPy's may differ in the
 behind one object (``_HostPasses``, ``_DevicePasses``), the driver between them reduces over the ranks -- the maximum of the
 weights, the number of draws, the extremes (``ranges=None``), and ONE sum of the int64 masses -- and the levels are computed after the
 sum, on every rank.  The result is identical, bin for bin, to one process over all draws."""
+import inspect
+
 import numpy as np
 
 from ._pipeline_data import host_f64
 
-__all__ = ['marginals', 'marginals_sharded', 'Marginals']
+__all__ = ['marginals', 'marginals_of_shard', 'marginals_sharded', 'Marginals']
 
 MAX_BINS, MAX_BINS2D = 1024, 128
 _U64 = np.uint64
@@ -484,6 +486,26 @@ def _make_passes(x, given, kind, params, d_all):
     return _HostPasses(xh if whole else xh[:, params], None if given is None else host_f64(given).reshape(-1), kind)
 
 
+def marginals_of_shard(x, log_weights=None, weights=None, collective=True, **options):
+    """``marginals`` of ALL ranks' draws, of which ``x`` (n, d) or (n_chain_local, n_draw, d), host or device, with its weights is
+    this rank's shard; ``options`` are those of ``marginals`` (``OPTIONS`` has the defaults).  With more than one rank a collective
+    that every rank calls (``marginals_sharded``); every rank returns the same ``Marginals``.  ``collective=False``: this process
+    alone, which a device shard allows only without a process group."""
+    unknown = set(options) - set(OPTIONS)
+    if unknown:
+        raise TypeError('unexpected options: %s.' % ', '.join(sorted(unknown)))
+    d_all = int(x.shape[-1])
+    given, kind = _weights_of(tuple(x.shape), log_weights, weights)
+    checked = _check_options(d_all, **dict(OPTIONS, **options))
+    if getattr(x, 'is_cuda', False):
+        from .. import _lib, parallel
+        if not collective and parallel.world()[1] > 1:
+            raise NotImplementedError('utils.marginals on a device tensor is single-process: TraceTuple.marginals is the collective.')
+        if len(checked[4]) and len(checked[3]) > _lib.MARG_MAX_LD:
+            raise NotImplementedError('pairs of more than %d parameters on the device route.' % _lib.MARG_MAX_LD)
+    return marginals_sharded(_make_passes(x, given, kind, checked[3], d_all), *checked, collective=collective)
+
+
 def marginals(x, log_weights=None, weights=None, bins=64, bins2d=64, ranges=None, params=None, pairs='all', probs=(0.68, 0.95)):
     """The marginal histograms of the draws x (n, d) or (n_chain, n_draw, d): a ``Marginals`` with the 1-D histograms of the columns
     ``params`` (default: all) at ``bins`` bins, the 2-D ones of ``pairs`` ('all': every i < j; None; or a list of pairs of positions
@@ -495,13 +517,9 @@ def marginals(x, log_weights=None, weights=None, bins=64, bins2d=64, ranges=None
         raise ValueError('x should be (n, d) or (n_chain, n_draw, d).')
     if int(np.prod(x.shape[:-1])) < 1 or x.shape[-1] < 1:
         raise ValueError('x is empty.')
-    given, kind = _weights_of(tuple(x.shape), log_weights, weights)
-    bins, bins2d, ranges, params, pairs, probs = _check_options(int(x.shape[-1]), bins, bins2d, ranges, params, pairs, probs)
-    if getattr(x, 'is_cuda', False):
-        from .. import _lib, parallel
-        if parallel.world()[1] > 1:
-            raise NotImplementedError('utils.marginals on a device tensor is single-process: TraceTuple.marginals is the collective.')
-        if len(pairs) and len(params) > _lib.MARG_MAX_LD:
-            raise NotImplementedError('pairs of more than %d parameters on the device route.' % _lib.MARG_MAX_LD)
-    return marginals_sharded(_make_passes(x, given, kind, params, int(x.shape[-1])), bins, bins2d, ranges, params, pairs, probs,
-                             collective=False)
+    return marginals_of_shard(x, log_weights, weights, collective=False, bins=bins, bins2d=bins2d, ranges=ranges, params=params,
+                              pairs=pairs, probs=probs)
+
+
+# the options and their defaults, as ``marginals`` declares them: bins, bins2d, ranges, params, pairs, probs
+OPTIONS = {name: p.default for name, p in list(inspect.signature(marginals).parameters.items())[3:]}

@@ -18,9 +18,9 @@ bimodal sample inflates: at Scott's factor two well separated Gaussians come wit
 through ``params`` and read ``n_minor``.  Plain mean shift converges linearly, at a rate of about 1 / (1 + factor^2) per iteration."""
 import numpy as np
 
-from .kde import kde, _host
+from .kde import kde, flat_draws, _host
 
-__all__ = ['modes', 'Modes']
+__all__ = ['modes', 'modes_by_chain', 'Modes']
 
 
 class Modes:
@@ -29,7 +29,7 @@ class Modes:
     x (K, d) the modes in the original coordinates (of the selected ``params``); logpdf (K,) the estimate's log density there;
     share, share_err (K,); label (n_seeds,) the mode of every seed, -1 where the iteration did not converge; seed_index
     (n_seeds,) the seeds' rows of the sample; n_iter the iterations made; n_not_converged; n_modes the modes with share >=
-    ``min_share`` and n_minor the others; factor the bandwidth factor of the estimate.  ``TraceTuple.modes`` adds chain_mode
+    ``min_share`` and n_minor the others; factor the bandwidth factor of the estimate.  ``modes_by_chain`` adds chain_mode
     (n_chain,), the majority label of a chain's seeds (ties to the lower label, -1 where none converged), and chain_split
     (n_chain,), whether the chain's converged seeds disagree."""
 
@@ -110,3 +110,33 @@ def modes(x, log_weights=None, params=None, n_seeds=1024, bw_method=None, bw_fac
     est = kde(x, bw_method=bw_method, bw_factor=bw_factor, log_weights=log_weights)
     rows = systematic_rows(_host(est.weights), n_seeds, np.random.default_rng(seed))
     return modes_from_seeds(est, rows, tol, max_iter, merge_tol, min_share)
+
+
+def modes_by_chain(x, log_weights=None, per_chain=4, params=None, seed=0, bw_method=None, bw_factor=None, **kw):
+    """``modes`` of the per-chain draws ``x`` (n_chain, n_t, d), host or device, seeded from every chain, and which chains sit in
+    which mode: ``per_chain`` evenly spaced draws of every chain or, with ``log_weights`` ((n_chain, n_t) or flat in that order),
+    ``per_chain`` rows resampled within the chain in proportion to the weights (a chain without weight seeds from its first draw).
+    ``kw`` are ``tol``, ``max_iter``, ``merge_tol`` and ``min_share``.  The ``Modes`` also has ``chain_mode`` and ``chain_split``."""
+    n_chain, n_t, per_chain = int(x.shape[0]), int(x.shape[1]), int(per_chain)
+    if per_chain < 1:
+        raise ValueError('per_chain should be at least 1.')
+    x, log_weights = flat_draws(x, log_weights, params)
+    est = kde(x, log_weights=log_weights, bw_method=bw_method, bw_factor=bw_factor)
+    if log_weights is None:
+        t = ((np.arange(per_chain) + 0.5) * n_t / per_chain).astype(np.int64)
+        rows = (np.arange(n_chain)[:, None] * n_t + t[None, :]).reshape(-1)
+    else:
+        rng = np.random.default_rng(seed)
+        w = _host(est.weights).reshape(n_chain, n_t)
+        rows = np.concatenate([c * n_t + (systematic_rows(w[c], per_chain, rng) if w[c].sum() > 0. else np.zeros(per_chain, np.int64))
+                               for c in range(n_chain)])
+    out = modes_from_seeds(est, rows, **kw)
+    label = out.label.reshape(n_chain, per_chain)
+    out.chain_mode = np.full(n_chain, -1, dtype=np.int64)
+    out.chain_split = np.zeros(n_chain, dtype=bool)
+    for c in range(n_chain):
+        got = label[c][label[c] >= 0]
+        if got.size:
+            out.chain_mode[c] = int(np.argmax(np.bincount(got)))     # the first of equal counts: the lower label
+            out.chain_split[c] = bool(np.any(got != got[0]))
+    return out
