@@ -12,6 +12,7 @@ from .core.sample import sample
 from .samplers import NTrace, HTrace, TNTrace, GaussianBase, TraceTuple
 from .utils import SystematicResampler, data_loo, pointwise_loo, DataLOO, reweight_moments, data_reweight, Reweighted
 from .utils import data_lgo, grouped_loo, group_whitening_of, DataLGO
+from .utils import power_scale, data_power_scale, PowerScale
 from .core.refit import select_fit_points, importance_weights
 from .transforms import SIT
 from .evidence import GBS, GIS, GHM, bridge, importance, harmonic
@@ -19,4 +20,4 @@ from .evidence import GBS, GIS, GHM, bridge, importance, harmonic
 __all__ = ['PolyConfig', 'PolyModel', 'FitReport', 'Surrogate', 'SurrogateDensity', 'Chi2PipelineDensity', 'GaussianLink', 'sample', 'NTrace', 'HTrace', 'TNTrace', 'GaussianBase', 'TraceTuple',
            'SystematicResampler', 'select_fit_points', 'importance_weights', 'SIT', 'GBS', 'GIS', 'GHM', 'bridge', 'importance',
            'harmonic', 'data_loo', 'pointwise_loo', 'DataLOO', 'reweight_moments', 'data_reweight', 'Reweighted',
-           'data_lgo', 'grouped_loo', 'group_whitening_of', 'DataLGO']
+           'data_lgo', 'grouped_loo', 'group_whitening_of', 'DataLGO', 'power_scale', 'data_power_scale', 'PowerScale']

@@ -144,6 +144,8 @@ SYMBOLS = {
     'bfhip_rw_work_bytes': (C.c_size_t, [C.c_long, C.c_int]),
     'bfhip_rw_finish': (C.c_int, [_vp, C.c_long, _vp, C.c_long, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_int, C.c_long,
                                   C.c_long, C.c_long, _vp, C.c_int, C.c_long, C.c_int, _vp, _vp, _vp, C.c_size_t]),
+    'bfhip_rw_weights': (C.c_int, [_vp, C.c_long, _vp, C.c_long, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_long, _vp]),
+    'bfhip_pscale_cjs': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, C.c_long, C.c_int, _vp, _vp]),
     'bfhip_igamc': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp]),
     'bfhip_lgo_accum': (C.c_int, [_vp, C.c_long, _vp, C.c_long, C.c_int, C.POINTER(C.c_int), _dp, C.c_uint, _vp, C.c_long]),
     'bfhip_lgo_finish': (C.c_int, [_vp, C.c_long, _vp, C.c_long, C.c_int, _dp, _dp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t]),
@@ -179,12 +181,22 @@ PLOO_ROWS = ('lpd', 'swe', 'waic', 'elpd_loo', 'khat', 'sigma', 'n_tail', 'cut',
 RW_ROWS = ('log_evidence_ratio', 'khat', 'sigma', 'n_tail', 'ess', 'flags', 'cut')   # BFHIP_RW_LER ...
 LGO_ROWS = ('chi2_base', 'chi2_lgo', 'ppp_base', 'ppp_lgo')   # BFHIP_LGO_CHI2_BASE ...; BFHIP_LGO_NOUT rows
 RW_SUMS = 8            # BFHIP_RW_SUMS: the out block's first row of sums; BFHIP_RW_NOUT(d) = RW_SUMS + 2 (1 + 2 d) rows
+RWW_ROWS = ('sum', 'khat', 'flags')   # BFHIP_RWW_SUM ...; BFHIP_RWW_NOUT = 4 rows
+RWW_NOUT = 4
+CJS_ROWS = ('J', 'bound', 'cjs', 'ks', 'flags')   # BFHIP_CJS_J ...; BFHIP_CJS_NOUT rows
+CJS_NOUT = 5
+PSCALE_TILE = 2048     # BFHIP_PSCALE_TILE: sorted positions per workgroup of bfhip_pscale_cjs
 WSTAT_TILE = 2048      # sorted positions per workgroup of bfhip_wstat_cumweights: its work buffer is ceil(n / 2048) doubles
 
 
 def psis_work_bytes(n):
     """BFHIP_PSIS_WORK_BYTES(n)"""
     return 16 * int(n) + 32768
+
+
+def pscale_work(n):
+    """BFHIP_PSCALE_WORK(n): doubles of bfhip_pscale_cjs's work buffer"""
+    return (int(n) + PSCALE_TILE - 1) // PSCALE_TILE * 352
 
 
 _lib = None

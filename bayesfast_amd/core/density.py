@@ -378,6 +378,12 @@ class Chi2PipelineDensity(SurrogateDensity):
         from ..utils.reweight import data_reweight
         return data_reweight(self, x, y_new, **kw)
 
+    def power_scale(self, x, **kw):
+        """Power-scaling sensitivity to the likelihood and to the prior at the ORIGINAL-space draws x, a GPU tensor (n_chain, n_draw,
+        d) or (n, d): ``bayesfast_amd.utils.data_power_scale(self, x, **kw)``, a ``PowerScale``."""
+        from ..utils.power_scale import data_power_scale
+        return data_power_scale(self, x, **kw)
+
     def data_log_ratio(self, x, y_new, **kw):
         """The (n_chain, n_draw, K) device tensor of l_k(x) = log L(x | y_k) - log L(x | y) at the ORIGINAL-space draws x:
         ``bayesfast_amd.utils.reweight.data_log_ratio(self, x, y_new, **kw)``."""

@@ -511,3 +511,4 @@ extern "C" int bfhip_wstat_quantiles(bfhip_ctx *ctx, long n, const uint64_t *key
 #include "bfhip_ploo.h"
 #include "bfhip_rw.h"
 #include "bfhip_lgo.h"
+#include "bfhip_pscale.h"

@@ -506,6 +506,14 @@ class TraceTuple:
         from ..utils.reweight import data_reweight
         return data_reweight(density, self._diag_input(since_iter, include_warmup, True, 'samples'), y_new, log_weights=log_weights, **kw)
 
+    def power_scale(self, density, log_weights=None, since_iter=None, include_warmup=False, **kw):
+        """Power-scaling sensitivity of ``density``, a ``Chi2PipelineDensity``, to its likelihood and its prior
+        (``bayesfast_amd.utils.data_power_scale``: a ``PowerScale``) at the original-space draws that ``get(since_iter, include_warmup,
+        flatten=False)`` selects, read where ``sample()`` left them; ``kw`` are ``alphas``, ``prior_each``, ``threshold``, ``max_bytes``
+        and ``batch_bytes``.  Device parts only; single process only, as ``data_loo``."""
+        from ..utils.power_scale import data_power_scale
+        return data_power_scale(density, self._diag_input(since_iter, include_warmup, True, 'samples'), log_weights=log_weights, **kw)
+
     def profile(self, density, since_iter=None, include_warmup=False, **kw):
         """Profiles (``bayesfast_amd.utils.profile``: a ``Profile``) of ``density``, a ``SurrogateDensity`` or ``Chi2PipelineDensity``:
         the maximisation starts at the posterior mean of the sampling-space draws that ``get(since_iter, include_warmup,

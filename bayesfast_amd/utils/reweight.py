@@ -158,7 +158,8 @@ def _host(x, l, log_weights):
 # ---- the device route ------------------------------------------------------------------------------------------------------------------
 class _Stages(PsisStages):
     """Base table and scenario batches on one set of draws x (n_chain, n_draw, d), a device tensor read in place: ``run(buf, nb)``
-    queues the three stages on an (n, 16) series buffer that holds -l, ``result()`` makes the one copy to the host."""
+    queues the three stages on an (n, 16) series buffer that holds -l, ``result()`` makes the one copy to the host.  ``w`` (n,) are
+    the base weights, ``wsum`` their ``bfhip_wstat_moments`` figures."""
 
     def __init__(self, ctx, x, log_weights):
         import torch
@@ -173,6 +174,7 @@ class _Stages(PsisStages):
         # the base table: bfhip_wstat_moments on batches of 16 parameters under the base weights
         w = torch.exp(lb) if lb is not None else torch.full((n,), 1. / n, dtype=torch.float64, device=x.device)
         work = ctx.empty((_lib.WSTAT_WORK,))
+        self.w = w
         self.wsum = ctx.empty((4,))
         _lib.check(lib.bfhip_wstat_moments(h, n, None, _ptr(w), _ptr(self.wsum), None, _ptr(work)))
         buf = ctx.empty((n, width))
@@ -200,6 +202,7 @@ class _Stages(PsisStages):
                                                  int(x.stride(0)), ldr, _ptr(x), int(x.dtype == torch.float32), 0, self.d, _ptr(self.centre),
                                                  _ptr(rw), _ptr(self.rw_work), self.rw_work.numel()))
         self.outs.append(rw)
+        return out, head, tail   # what a further stage of the batch shares with the three (power_scale.py: bfhip_rw_weights)
 
     def result(self):
         d, r0 = self.d, self._lib.RW_SUMS

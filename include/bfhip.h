@@ -38,7 +38,9 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_TREEDEPTH 12
 
 /* 114: bfhip_kde_wmean (and bfhip_kde_wmean_work_bytes), the kernel-weighted means over the pairs of bfhip_kde_logsum: the score of the
- * estimate, kernel regression and the mean-shift step (additions only).
+ * estimate, kernel regression and the mean-shift step (additions only).  bfhip_rw_weights, the smoothed weights of a batch of columns of log
+ * ratios written out after the first two bfhip_ploo_* stages, and bfhip_pscale_cjs, the distance between two weighted ECDFs of one
+ * parameter for 16 weight columns at once: power-scaling sensitivity (additions only: the number stays).
  * 113: bfhip_kde_logsum (and bfhip_kde_work_bytes), the pairwise log-sum-exp of Gaussian kernels behind the multivariate kernel density
  * estimate and the parameter-shift test (additions only).
  * 112: bfhip_profile_lines and bfhip_pipeline_profile_lines, profiles of the density along grid lines: the device Newton maximiser
@@ -754,6 +756,51 @@ int bfhip_rw_finish(bfhip_ctx *ctx, long n, const double *series, long ld, int n
                     const uint64_t *tail_keys, const uint32_t *tail_idx, const double *out, void *work, size_t work_bytes, int n_chain,
                     long n_draw, long ldw, long ldr, const void *x, int is_f32, long since, int d, const double *centre, double *rw_out,
                     void *rw_work, size_t rw_work_bytes);
+
+/* Power-scaling sensitivity (bayesfast_amd/utils/power_scale.py has the definitions): the smoothed weights themselves, and the
+ * distance between two weighted ECDFs of one parameter for a batch of weight columns.
+ * bfhip_rw_weights: a fourth stage after bfhip_ploo_moments and bfhip_ploo_tail, before or after bfhip_rw_finish, with their arguments
+ *   (out, tail_keys and tail_idx are only read; work is their work buffer).  u (n, ld_u), ld_u >= nb, a buffer of its own that
+ *   overlaps none of the others: u[s ld_u + b] <- e_s / sum over the rows of the sample of e, e = exp(smoothed shifted r) -- rows not
+ *   above the cut pair with their own ratio, the M tail rows scattered by index with the smoothed values of the very launches of
+ *   bfhip_rw_finish -- and 0 in a row with lb = -inf.  In a column with flag 1 or 4 the rows of the sample are NaN.  Columns nb .. of u
+ *   are not written.  wout (BFHIP_RWW_NOUT, BFHIP_DIAG_BATCH): the sum, khat and the flags of bfhip_rw_finish, bit for bit.  The sum is
+ *   taken in an order fixed by n alone: bitwise repeatable in any slot of any batch.
+ * bfhip_pscale_cjs: one parameter, given by keys_sorted and order (n,) of bfhip_diag_sort on a column of bfhip_wstat_columns under the
+ *   base weights w (n,), and wsum of bfhip_wstat_moments (wsum[2] = n_pos, the rows of the sample: the first n_pos sorted positions),
+ *   against nb <= BFHIP_DIAG_BATCH columns of weights u (n, ld_u), ld_u >= nb.  With P and Q the running sums of w and u over the sorted
+ *   positions (Q - P is the running sum of u - w) and h_p = x_(p+1) - x_(p), p <= n_pos - 2:
+ *     out (BFHIP_CJS_NOUT, BFHIP_DIAG_BATCH) rows  BFHIP_CJS_J      sum h [P log2(P / M) + Q log2(Q / M)], M = (P + Q) / 2, as
+ *                                                                   M [(1 - t) log1p(-t) + (1 + t) log1p(t)] / ln 2, t = (Q - P) / (P + Q)
+ *                                                                   (its even series below |t| = 1/8)
+ *                                                  BFHIP_CJS_BOUND  sum h (P + Q)
+ *                                                  BFHIP_CJS_CJS    sqrt(J / bound)
+ *                                                  BFHIP_CJS_KS     max over h_p > 0 of |P - Q|
+ *                                                  BFHIP_CJS_FLAGS  1 a non-finite draw among the rows of the sample, 2 bound == 0
+ *                                                                   (either: cjs and ks are NaN)
+ *   Columns nb .. of out are not written.  Four launches: the 17 sums (w and the 16 columns of u - w) of tiles of BFHIP_PSCALE_TILE
+ *   sorted positions, sixteen lanes to a row of u; their scan by ONE workgroup; the pass that forms every position's terms; the tiles'
+ *   partial results reduced by ONE workgroup.  No workgroup waits on another, no atomics, every order fixed by n alone, and a column
+ *   never meets its neighbours: bitwise repeatable in any slot.  work: BFHIP_PSCALE_WORK(n) doubles.
+ * Stream-ordered, no host synchronisation. */
+#define BFHIP_RWW_NOUT 4
+#define BFHIP_RWW_SUM 0       /* sum of e over the rows of the sample */
+#define BFHIP_RWW_KHAT 1
+#define BFHIP_RWW_FLAGS 2     /* as BFHIP_RW_FLAGS; row 3 is spare */
+#define BFHIP_CJS_NOUT 5
+#define BFHIP_CJS_J 0
+#define BFHIP_CJS_BOUND 1
+#define BFHIP_CJS_CJS 2
+#define BFHIP_CJS_KS 3
+#define BFHIP_CJS_FLAGS 4
+#define BFHIP_PSCALE_TILE 2048
+#define BFHIP_PSCALE_TILE_WORK 352   /* doubles per tile: 17 tile sums, 16 x 17 slice sums, 3 x 16 partial results, padding */
+#define BFHIP_PSCALE_WORK(n) ((((size_t)(n) + BFHIP_PSCALE_TILE - 1) / BFHIP_PSCALE_TILE) * BFHIP_PSCALE_TILE_WORK)
+int bfhip_rw_weights(bfhip_ctx *ctx, long n, const double *series, long ld, int nb, int mode, const double *c, const double *lb,
+                     const uint64_t *tail_keys, const uint32_t *tail_idx, const double *out, void *work, size_t work_bytes, double *u,
+                     long ld_u, double *wout);
+int bfhip_pscale_cjs(bfhip_ctx *ctx, long n, const uint64_t *keys_sorted, const uint32_t *order, const double *wsum, const double *w,
+                     const double *u, long ld_u, int nb, double *out, double *work);
 
 /* Leave-group-out cross-validation of a batch of nb <= BFHIP_DIAG_BATCH groups of data points (bayesfast_amd/utils/data_lgo.py has the
  * definitions).  A group's column of the (n, BFHIP_DIAG_BATCH) series buffer holds ell_s = c - q_s / 2, q_s the conditional chi-square
