@@ -153,7 +153,9 @@ __global__ __launch_bounds__(AC_TH) void bf_acor_lag_kernel(int n_w, long n_t, i
             for (int wv = 0; wv < AC_WAVES; ++wv) sm += red[(r * AC_WAVES + wv) * 64 + ln];
         }
         const long t = l0 + lag;
-        if (t < n_lag && k0 + kk < n_d) part[((long)g * n_lag + t) * n_d + k0 + kk] = sm;
+        // a lag >= n_t has no terms: 0, also where the tile's earlier lags are live and sm is 0 * inf or 0 * NaN (a constant or a
+        // non-finite series), as in a tile wholly beyond the series
+        if (t < n_lag && k0 + kk < n_d) part[((long)g * n_lag + t) * n_d + k0 + kk] = (tb + lag < n_t) ? sm : 0.;
     }
 }
 

@@ -581,8 +581,13 @@ int bfhip_polar_ns(bfhip_ctx *ctx, int d, const double *a, double *x, int n_iter
  * every walker's block row-major and contiguous.  y_wk(s) = x_wk(s) - mean_wk, a_wk(t) = sum_{s < n_t - t} y_wk(s) y_wk(s + t).
  *   bfhip_acor_moments   mean (n_w, n_d) <- mean_wk; inv (n_w, n_d) <- 1 / a_wk(0), both by two passes over time (a constant series
  *                        has inv = inf, and its lag sums are NaN, as the host port's 0 / 0)
- *   bfhip_acor_lag_sums  out (n_lag, n_d) <- sum_w a_wk(t0 + i) inv_wk for i < n_lag (0 for lags >= n_t); mean and inv from
- *                        bfhip_acor_moments.  work: min(n_w, 256) n_lag n_d doubles (per-walker-group partial sums).
+ *   bfhip_acor_lag_sums  out (n_lag, n_d) <- sum_w a_wk(t0 + i) inv_wk for i < n_lag (exactly +0 for lags >= n_t, whatever the
+ *                        series holds); mean and inv from bfhip_acor_moments.  work: min(n_w, 256) n_lag n_d doubles
+ *                        (per-walker-group partial sums).  A series with a NaN or an infinite sample has NaN moments, and its
+ *                        column is NaN at every lag < n_t.  With a finite mean supplied by the caller instead, such a sample
+ *                        makes NaN every lag whose sum contains it, and may make NaN any other lag < n_t of its column (the
+ *                        zero padding past the series' end multiplies it): which of those is not part of the contract, and
+ *                        the independence of the block below does not cover them.  Other columns are never touched by it.
  * The window search (rho_k = out / n_w, tau_k(t) = 2 sum rho_k - 1, the first t >= c tau_k(t)) is the caller's: it asks for lag
  * blocks until every window has closed.  n_d >= 1 of any size (BFHIP_MAX_DIM does not apply); NaN propagates.  Every sum has a
  * fixed order set by (n_w, n_t, n_d) alone: bitwise repeatable, and a lag's sum does not depend on the block that computes it.
