@@ -127,6 +127,7 @@ SYMBOLS = {
     'bfhip_logmeanexp_stats': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp, _vp]),
     'bfhip_acor_moments': (C.c_int, [_vp, C.c_int, C.c_long, C.c_int, C.c_long, _vp, _vp, _vp]),
     'bfhip_acor_lag_sums': (C.c_int, [_vp, C.c_int, C.c_long, C.c_int, C.c_long, _vp, _vp, _vp, C.c_long, C.c_int, _vp, _vp]),
+    'bfhip_health_chains': (C.c_int, [_vp, C.c_int, C.c_long, C.c_long, _vp, C.c_int, C.c_int, _vp, _vp]),
     'bfhip_diag_columns': (C.c_int, [_vp, C.c_int, C.c_long, C.c_long, C.c_long, _vp, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, _vp,
                                      _vp]),
     'bfhip_diag_extent': (C.c_int, [_vp, C.c_int, C.c_long, _vp, _vp, _vp]),
@@ -170,6 +171,10 @@ PROFILE_SAMPLING, PROFILE_ORIGINAL, PROFILE_NOT_RUN = 0, 1, 4   # BFHIP_PROFILE_
 WSUM_MAX = 7            # BFHIP_WSUM_MAX: values bfhip_wave_sum_probe reduces together
 WSUM_FORMS = {'built': 0, 'packed': 1, 'unpacked': 2}   # BFHIP_WSUM_BUILT / _PACKED / _UNPACKED
 ACOR_MAX_GROUPS = 256   # walker groups of bfhip_acor_lag_sums: its work buffer is min(n_w, 256) * n_lag * n_d doubles
+HEALTH_I = ('n_divergent', 'n_max_treedepth', 'n_leapfrog', 'max_tree_size', 'n_accepted', 'n_nonfinite', 'n_moved')   # BFHIP_HEALTH_I_*; then the depth histogram
+HEALTH_I_N = len(HEALTH_I) + MAX_TREEDEPTH + 1   # BFHIP_HEALTH_I_N
+HEALTH_F = ('mean_accept', 'logp_mean', 'logp_var', 'energy_mean', 'energy_var', 'bfmi', 'step_size')   # BFHIP_HEALTH_F_*
+HEALTH_F_N = len(HEALTH_F)   # BFHIP_HEALTH_F_N
 DIAG_BATCH = 16         # BFHIP_DIAG_BATCH: parameters per batch of the bfhip_diag_* passes (the width of their series buffers)
 WSTAT_WORK = 65536      # BFHIP_WSTAT_WORK: doubles of bfhip_wstat_moments' work buffer
 MARG_MAX_BINS, MARG_MAX_BINS2D, MARG_MAX_LD = 1024, 128, 256   # BFHIP_MARG_MAX_BINS / _BINS2D / _LD

@@ -18,7 +18,8 @@ reference's classes (the bases are taken from the imported package at call time;
                        chain, built lazily) whose ``step_size`` is a ``DualAverageAdaptation`` and whose ``metric`` is a
                        ``QuadMetric*`` carrying the adapted state, so ``_get_step_size`` / ``_get_metric`` accept them.  Every
                        analysis reader that ``bayesfast_amd.TraceTuple.READERS`` names (``rhat``, ``summary``, ``marginals``,
-                       ``kde``, ``modes`` ...) is forwarded to the device result, from that one list.
+                       ``kde``, ``modes`` ...) is forwarded to the device result, from that one list, and so is ``health``
+                       (``TraceTuple.SAMPLER_READERS``: did the sampler itself work).
 * ``sample``           the signature of ``bayesfast.core.sample.sample``: takes the reference's ``Density`` (read by duck
                        typing, ``adapters.py``) and the reference's ``NTrace`` / ``HTrace`` / dict / a ``TraceTuple`` returned
                        earlier (continue the chains), runs all chains in fused device launches.
@@ -275,7 +276,7 @@ def reference_classes(bayesfast=None):
 
         __call__ = get
 
-        # ---- the analysis readers of the device result (``bayesfast_amd.TraceTuple.READERS``; the reference's TraceTuple has none)
+        # ---- the analysis readers of the device result (``bayesfast_amd.TraceTuple.READERS`` and ``.SAMPLER_READERS``; the reference's TraceTuple has none)
         # are attached below the class ----
 
         # ---- per-chain traces of the reference's own classes, for _get_step_size / _get_metric / users ----
@@ -340,7 +341,7 @@ def reference_classes(bayesfast=None):
         reader.__name__, reader.__doc__ = name, getattr(_our_st.TraceTuple, name).__doc__
         return reader
 
-    for name in _our_st.TraceTuple.READERS:
+    for name in _our_st.TraceTuple.READERS + _our_st.TraceTuple.SAMPLER_READERS:
         setattr(TraceTuple, name, _forward(name))
 
     ref_laplace = bf.utils.laplace

@@ -260,6 +260,9 @@ class TraceTuple:
     READERS = ('integrated_time', 'rhat', 'ess', 'summary', 'weighted_summary', 'predictive', 'data_loo', 'data_lgo', 'data_reweight',
                'profile', 'marginals', 'kde', 'modes', 'parameter_shift')
 
+    # the readers of the sampler's own statistics (forwarded by ``integrate.py`` as well)
+    SAMPLER_READERS = ('health',)
+
     def __init__(self, trace, samples, stats, samples_original, logp_original, chains=None, stats_t=None):
         self._trace = trace
         self.sampler = trace._sampler
@@ -573,6 +576,55 @@ class TraceTuple:
         if isinstance(other, TraceTuple):
             other = other._view(since_iter, include_warmup, original_space)
         return parameter_shift(x, other, log_weights_a=log_weights, log_weights_b=log_weights_other, **kw)
+
+    def health(self, since_iter=None, include_warmup=False, original_space=True, stats=None, **thresholds):
+        """Did the sampler itself work (``bayesfast_amd.utils.sampler_health``: a ``SamplerHealth``): divergent transitions,
+        transitions that hit the tree-depth limit, E-BFMI and the chains that look stuck, over the rows that ``get(since_iter,
+        include_warmup, original_space, flatten=False)`` selects, read off the statistics table and the draws where ``sample()``
+        left them (device parts take the device route).  The sampler's layout and ``max_treedepth`` come from the trace (TNUTS is
+        read as NUTS); ``thresholds`` are ``bfmi_min``, ``z_max`` and ``var_ratio_min``.  Under ``torch.distributed`` with more than
+        one rank a collective, to be called by every rank: every rank gets the ``SamplerHealth`` of ALL chains, bit for bit that
+        of one process, and only the two per-chain tables cross between ranks (no ``gather()``); ``stats``, if a dict, receives
+        'collectives' and 'wire_bytes'."""
+        from ..utils.health import sampler_health_sharded
+        since = self._start(since_iter, include_warmup)
+        h = sampler_health_sharded(self._parts['stats'][:, since:], self._view(since, False, original_space), self.n_chain,
+                                   sampler=self.sampler, max_treedepth=getattr(self._trace, 'max_treedepth', 10), stats=stats,
+                                   **thresholds)
+        h._selection = (since, bool(original_space))
+        return h
+
+    def select_chains(self, index_or_mask):
+        """A new ``TraceTuple`` over the chosen chains (indices, or a boolean mask of n_chain entries: ``tt.select_chains(~h.flagged)``
+        leaves out what ``health()`` flagged), every part ``index_select``-ed where it lives and the trace a shallow copy with
+        ``n_chain`` set; the result does not carry the chains' device state (``_chains`` is None), so it can be read but not
+        continued.  Single process only: with more than one rank it raises ``NotImplementedError``."""
+        self._single_process('the chains of this TraceTuple are spread over the ranks: call gather() on every rank and select among the '
+                             'host arrays, tt.gather().get(flatten=False)[index].')
+        import copy
+        idx = np.asarray(index_or_mask)
+        if idx.dtype == bool:
+            if idx.shape != (self.n_chain,):
+                raise ValueError('a mask should have n_chain entries.')
+            idx = np.flatnonzero(idx)
+        idx = idx.astype(np.int64).reshape(-1)
+        if idx.size == 0:
+            raise ValueError('no chain is selected.')
+        if idx.min() < -self.n_chain or idx.max() >= self.n_chain:
+            raise IndexError('chain index out of range.')
+        idx = np.where(idx < 0, idx + self.n_chain, idx)
+
+        def take(t):
+            if isinstance(t, np.ndarray):
+                return t[idx]
+            import torch
+            return t.index_select(0, torch.as_tensor(idx, device=t.device))
+        parts = {k: take(v) for k, v in self._parts.items() if not (k == 'samples_original' and v is self._parts['samples'])}
+        parts.setdefault('samples_original', parts['samples'])
+        trace = copy.copy(self._trace)
+        trace.n_chain = int(idx.size)
+        return TraceTuple(trace, parts['samples'], parts['stats'], parts['samples_original'], parts['logp_original'], chains=None,
+                          stats_t=parts.get('stats_t'))
 
     def __getitem__(self, key):
         return self.sample_traces[key]

@@ -37,7 +37,9 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_DIM 128         /* input_size limit of the device path */
 #define BFHIP_MAX_TREEDEPTH 12
 
-/* 114: bfhip_kde_wmean (and bfhip_kde_wmean_work_bytes), the kernel-weighted means over the pairs of bfhip_kde_logsum: the score of the
+/* 115: bfhip_health_chains, the per-chain sampler health figures (divergences, tree-depth limit, E-BFMI, depth histogram) read off the
+ * statistics table in place (additions only).
+ * 114: bfhip_kde_wmean (and bfhip_kde_wmean_work_bytes), the kernel-weighted means over the pairs of bfhip_kde_logsum: the score of the
  * estimate, kernel regression and the mean-shift step (additions only).  bfhip_rw_weights, the smoothed weights of a batch of columns of log
  * ratios written out after the first two bfhip_ploo_* stages, and bfhip_pscale_cjs, the distance between two weighted ECDFs of one
  * parameter for 16 weight columns at once: power-scaling sensitivity (additions only: the number stays).
@@ -596,6 +598,46 @@ int bfhip_polar_ns(bfhip_ctx *ctx, int d, const double *a, double *x, int n_iter
 int bfhip_acor_moments(bfhip_ctx *ctx, int n_w, long n_t, int n_d, long ldw, const double *x, double *mean, double *inv);
 int bfhip_acor_lag_sums(bfhip_ctx *ctx, int n_w, long n_t, int n_d, long ldw, const double *x, const double *mean, const double *inv,
                         long t0, int n_lag, double *work, double *out);
+
+/* Did the sampler itself work (bayesfast_amd/utils/health.py, sampler_health: the divergent transitions, the transitions that hit
+ * the tree-depth limit and Betancourt's E-BFMI that Stan, PyMC and ArviZ warn about): the per-chain figures, in one launch, from
+ * the statistics table as bfhip_sampler_run left it.
+ * stats: the FIRST SELECTED ROW of chain 0; chain c's n_rows rows of BFHIP_STAT_STRIDE float64 start at stats + c ldc and are
+ * contiguous (ldc >= n_rows BFHIP_STAT_STRIDE doubles, free for one chain), so that a [:, since:] view of a longer table goes in as
+ * it is.  sampler: 0 = NUTS (the BFHIP_NS_* columns), 1 = HMC (BFHIP_HS_*).  1 <= max_treedepth <= BFHIP_MAX_TREEDEPTH.
+ *   out_i (n_chain, BFHIP_HEALTH_I_N) int64, exact:
+ *     N_DIVERGENT       rows with diverging != 0
+ *     N_MAX_TREEDEPTH   NUTS: rows with tree_depth >= max_treedepth; HMC: 0
+ *     N_LEAPFROG        sum of tree_size (HMC: of n_int_step); an entry that is no positive number below 2^52 counts as 0
+ *     MAX_TREE_SIZE     the largest of them
+ *     N_ACCEPTED        HMC: rows with accepted != 0; NUTS: 0
+ *     N_NONFINITE       rows whose logp or energy is not finite
+ *     N_MOVED           rows i >= 1 whose logp differs from that of row i - 1 (0: the chain never moved; an exact test, where
+ *                       the centred sum of squares of n copies of a constant depends on how their sum rounds)
+ *     DEPTH_HIST + b    NUTS: rows with tree_depth in [b, b + 1), b = 0 .. BFHIP_MAX_TREEDEPTH; a depth outside [0,
+ *                       BFHIP_MAX_TREEDEPTH] (or NaN) is counted in the last bin; HMC: 0
+ *   out_f (n_chain, BFHIP_HEALTH_F_N) float64:
+ *     MEAN_ACCEPT       mean of mean_tree_accept (HMC: of accept_stat)
+ *     LOGP_MEAN, LOGP_VAR, ENERGY_MEAN, ENERGY_VAR   the variances unbiased (n_rows - 1), each a second pass about its mean
+ *     BFMI              sum_{i >= 1} (E_i - E_{i-1})^2 / sum_i (E_i - mean E)^2 (a constant energy: NaN, the 0 / 0 it stands for, whatever
+ *                       the rounding of the mean leaves in the denominator)
+ *     STEP_SIZE         step_size of the last selected row
+ *   A chain with N_NONFINITE > 0 has NaN in its five moments and BFMI (MEAN_ACCEPT and STEP_SIZE are what the table holds); no
+ *   other chain is touched by it.
+ * One workgroup per chain; every sum has an order set by n_rows alone, so a chain's outputs are the same bits alone or in any
+ * launch, at any chain index.  n_chain >= 1, 2 <= n_rows <= 2^38.  Work: the selected rows are read twice (the second time from
+ * cache).  Stream-ordered, no host synchronisation, no atomics. */
+enum {
+    BFHIP_HEALTH_I_N_DIVERGENT = 0, BFHIP_HEALTH_I_N_MAX_TREEDEPTH, BFHIP_HEALTH_I_N_LEAPFROG, BFHIP_HEALTH_I_MAX_TREE_SIZE,
+    BFHIP_HEALTH_I_N_ACCEPTED, BFHIP_HEALTH_I_N_NONFINITE, BFHIP_HEALTH_I_N_MOVED, BFHIP_HEALTH_I_DEPTH_HIST,
+    BFHIP_HEALTH_I_N = BFHIP_HEALTH_I_DEPTH_HIST + BFHIP_MAX_TREEDEPTH + 1
+};
+enum {
+    BFHIP_HEALTH_F_MEAN_ACCEPT = 0, BFHIP_HEALTH_F_LOGP_MEAN, BFHIP_HEALTH_F_LOGP_VAR, BFHIP_HEALTH_F_ENERGY_MEAN,
+    BFHIP_HEALTH_F_ENERGY_VAR, BFHIP_HEALTH_F_BFMI, BFHIP_HEALTH_F_STEP_SIZE, BFHIP_HEALTH_F_N
+};
+int bfhip_health_chains(bfhip_ctx *ctx, int n_chain, long n_rows, long ldc, const double *stats, int sampler, int max_treedepth,
+                        long long *out_i, double *out_f);
 
 /* Convergence diagnostics of many chains (rank-normalised split-R-hat, bulk / tail / mean effective sample size and the table of
  * mean, sd and quantiles: Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021; bayesfast_amd/utils/diagnostics.py holds the
