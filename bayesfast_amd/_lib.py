@@ -121,6 +121,9 @@ SYMBOLS = {
     'bfhip_kde_wmean_work_bytes': (C.c_size_t, [C.c_long, C.c_long, C.c_int, C.c_int]),
     'bfhip_kde_wmean': (C.c_int, [_vp, C.c_int, C.c_long, _vp, C.c_long, _vp, C.c_int, _vp, C.c_long, C.c_long, _vp, C.c_long, C.c_int, _vp, _vp,
                                   C.c_long, _vp, C.c_size_t]),
+    'bfhip_gmm_work_bytes': (C.c_size_t, [C.c_long, C.c_int, C.c_int]),
+    'bfhip_gmm_step': (C.c_int, [_vp, C.c_int, C.c_int, C.c_long, _vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_long, _vp,
+                                 C.c_size_t]),
     'bfhip_spline_apply': (C.c_int, [_vp, C.c_int, C.c_long, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     'bfhip_bridge_sums': (C.c_int, [_vp, C.c_long, _vp, C.c_long, _vp, C.c_double, _vp]),
     'bfhip_bridge_terms': (C.c_int, [_vp, C.c_long, _vp, _vp, C.c_long, _vp, _vp, C.c_double, _vp, _vp]),

@@ -89,7 +89,7 @@ extern "C" int bfhip_debug_buffer(const char *key, void *device_ptr) {
 }
 extern "C" const char *bfhip_debug_last_kernel(void) { return bf_tune().last_kernel; }
 
-extern "C" int bfhip_version(void) { return 115; }   // 115: bfhip_health_chains (the per-chain sampler health figures off the statistics table); 114: bfhip_kde_wmean, bfhip_kde_wmean_work_bytes (kernel-weighted means over the pairs of bfhip_kde_logsum: score, kernel regression, mean shift); 113: bfhip_kde_logsum, bfhip_kde_work_bytes (the pairwise log-sum-exp of Gaussian kernels: multivariate KDE, parameter shift); 112: bfhip_profile_lines, bfhip_pipeline_profile_lines (profiles of the density along grid lines: masked Newton maximisations in continuation); 110: bfhip_polymodel_columns (a batch of the polymodel's outputs at draws read in place from the chain tensor, and the bound radius); 109: bfhip_lstsq_loo (leverages, leave-one-out residuals and their sums from the fit's kept factor); 108: bfhip_wave_packs_probe (the 64-lane sums left in their vector registers: the values read one by one and the any-value-not-positive test); 107: bfhip_pipeline_logp_hess, bfhip_pipeline_laplace_opt (analytic and Gauss-Newton Hessian of the pipeline density, its device Newton maximiser); 106: bfhip_wave_sum_probe (the kernels' 64-lane sums on given lane values); 105: bfhip_diag_columns, bfhip_diag_extent, bfhip_diag_sort, bfhip_diag_rank (split-R-hat, ESS, posterior summary); 104: bfhip_logp_hess, bfhip_laplace_opt (analytic Hessian, device Newton maximiser); 103: bfhip_acor_moments, bfhip_acor_lag_sums (device integrated_time); 102: bfhip_polar_ns work = 2 d^2 + n_iter + 10 doubles; 101: BFHIP_TREE_MODE_WORK 4162 (was 4098), work[0] = size | laggard << 12
+extern "C" int bfhip_version(void) { return 116; }   // 116: bfhip_gmm_step, bfhip_gmm_work_bytes (one EM pass of a Gaussian mixture over the draws: log density, responsibilities, weighted moments); 115: bfhip_health_chains (the per-chain sampler health figures off the statistics table); 114: bfhip_kde_wmean, bfhip_kde_wmean_work_bytes (kernel-weighted means over the pairs of bfhip_kde_logsum: score, kernel regression, mean shift); 113: bfhip_kde_logsum, bfhip_kde_work_bytes (the pairwise log-sum-exp of Gaussian kernels: multivariate KDE, parameter shift); 112: bfhip_profile_lines, bfhip_pipeline_profile_lines (profiles of the density along grid lines: masked Newton maximisations in continuation); 110: bfhip_polymodel_columns (a batch of the polymodel's outputs at draws read in place from the chain tensor, and the bound radius); 109: bfhip_lstsq_loo (leverages, leave-one-out residuals and their sums from the fit's kept factor); 108: bfhip_wave_packs_probe (the 64-lane sums left in their vector registers: the values read one by one and the any-value-not-positive test); 107: bfhip_pipeline_logp_hess, bfhip_pipeline_laplace_opt (analytic and Gauss-Newton Hessian of the pipeline density, its device Newton maximiser); 106: bfhip_wave_sum_probe (the kernels' 64-lane sums on given lane values); 105: bfhip_diag_columns, bfhip_diag_extent, bfhip_diag_sort, bfhip_diag_rank (split-R-hat, ESS, posterior summary); 104: bfhip_logp_hess, bfhip_laplace_opt (analytic Hessian, device Newton maximiser); 103: bfhip_acor_moments, bfhip_acor_lag_sums (device integrated_time); 102: bfhip_polar_ns work = 2 d^2 + n_iter + 10 doubles; 101: BFHIP_TREE_MODE_WORK 4162 (was 4098), work[0] = size | laggard << 12
 extern "C" const char *bfhip_last_error(void) { return g_err; }
 
 extern "C" int bfhip_ctx_create(bfhip_ctx **out, int device, void *stream) {

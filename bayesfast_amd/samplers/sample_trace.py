@@ -561,6 +561,24 @@ class TraceTuple:
                              'gather the chains and use the host port, utils.modes(tt.gather().get(flatten=True)).')
         return modes_by_chain(self._view(since_iter, include_warmup, original_space), log_weights, per_chain, **kw)
 
+    def gmm(self, n_components=2, log_weights=None, since_iter=None, include_warmup=False, original_space=True, **kw):
+        """The Gaussian mixture (``bayesfast_amd.utils.gmm``: a ``GaussianMixture``) fitted by EM to the draws that ``get(since_iter,
+        include_warmup, original_space, flatten=True)`` selects (device parts take the device route and stay on the device; as in
+        ``kde``, a selection that leaves out leading iterations is copied once per call into one (n, d) matrix, not per
+        iteration), and which chains sit in which component.  ``n_components`` may be a sequence (the fit of lowest BIC is returned);
+        ``log_weights``, if given, holds one log weight per selected draw, shaped (n_chain, n_t) or flat in that order; ``kw`` are
+        ``params``, ``n_init``, ``seed``, ``tol``, ``max_iter``, ``reg_covar``, ``means_init``, ``weights_init``,
+        ``covariances_init`` and ``check_every``.  The result also has ``chain_share`` (n_chain, K), the mean responsibility of a
+        chain's draws, ``chain_component`` (n_chain,), its argmax, and ``chain_split`` (n_chain,), set where the chain's largest
+        share is below 0.9.  Single process only: with more than one rank it raises ``NotImplementedError``."""
+        from ..utils.gmm import gmm
+        self._single_process('the mixture is fitted to the draws of ALL chains, and this TraceTuple holds one rank\'s: '
+                             'gather the chains and use the host port, utils.gmm(tt.gather().get(flatten=False)).')
+        x = self._view(since_iter, include_warmup, original_space)
+        out = gmm(x, n_components, log_weights=log_weights, **kw)
+        out.chain_share, out.chain_component, out.chain_split = out.component_of_chain(x.shape[:2])
+        return out
+
     def parameter_shift(self, other, log_weights=None, log_weights_other=None, since_iter=None, include_warmup=False,
                         original_space=True, **kw):
         """The parameter-difference test (``bayesfast_amd.utils.parameter_shift``: a ``ParameterShift``) between the draws that

@@ -12,6 +12,7 @@ from .profile import profile, Profile, ProfileInterval
 from .kde import kde
 from .shift import parameter_shift, ParameterShift
 from .modes import modes, Modes
+from .gmm import gmm, GaussianMixture, gmm_step
 from .power_scale import power_scale, data_power_scale, PowerScale
 from .health import sampler_health, sampler_health_sharded, divergent_summary, SamplerHealth, DivergentSummary
 
@@ -20,4 +21,4 @@ __all__ = ['SystematicResampler', 'integrated_time', 'AutocorrError', 'Laplace',
            'pointwise_loo', 'DataLOO', 'reweight_moments', 'data_reweight', 'Reweighted', 'profile', 'Profile', 'ProfileInterval',
            'data_lgo', 'grouped_loo', 'group_whitening_of', 'DataLGO', 'kde', 'parameter_shift', 'ParameterShift', 'modes', 'Modes',
            'power_scale', 'data_power_scale', 'PowerScale', 'sampler_health', 'sampler_health_sharded', 'divergent_summary', 'SamplerHealth',
-           'DivergentSummary']
+           'DivergentSummary', 'gmm', 'GaussianMixture', 'gmm_step']

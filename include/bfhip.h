@@ -37,7 +37,9 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_DIM 128         /* input_size limit of the device path */
 #define BFHIP_MAX_TREEDEPTH 12
 
-/* 115: bfhip_health_chains, the per-chain sampler health figures (divergences, tree-depth limit, E-BFMI, depth histogram) read off the
+/* 116: bfhip_gmm_step (and bfhip_gmm_work_bytes), one EM iteration's pass over the draws for a Gaussian mixture: log density,
+ * responsibilities and the weighted moments of every component (additions only).
+ * 115: bfhip_health_chains, the per-chain sampler health figures (divergences, tree-depth limit, E-BFMI, depth histogram) read off the
  * statistics table in place (additions only).
  * 114: bfhip_kde_wmean (and bfhip_kde_wmean_work_bytes), the kernel-weighted means over the pairs of bfhip_kde_logsum: the score of the
  * estimate, kernel regression and the mean-shift step (additions only).  bfhip_rw_weights, the smoothed weights of a batch of columns of log
@@ -514,6 +516,38 @@ int bfhip_kde_logsum(bfhip_ctx *ctx, int d, long n, const double *z, long ldz, c
 size_t bfhip_kde_wmean_work_bytes(long n, long m, int d, int k);
 int bfhip_kde_wmean(bfhip_ctx *ctx, int d, long n, const double *z, long ldz, const double *logw, int k, const double *v, long ldv, long m,
                     const double *zq, long ldq, int exclude_self, double *logsum, double *mean, long ldo, void *work, size_t work_bytes);
+
+/* One pass of expectation-maximisation for a mixture of k Gaussians over n draws: the E step and the sufficient statistics of the M
+ * step (nothing in the reference; bayesfast_amd/utils/gmm.py).  With t_ik = logc[k] - |(x_i - mean_k) A_k|^2 / 2:
+ *     logpdf[i] = log sum_k exp(t_ik),   resp[i][k] = exp(t_ik - logpdf[i]),
+ * a true log-sum-exp with a running maximum: a row so far from every component that every exp(t_ik) underflows still has a finite
+ * logpdf and responsibilities that sum to 1.  The energy is formed from the DIFFERENCE x_i - mean_k, subtracted before the product
+ * with A_k; the quadratic form is not expanded, so a component far from the origin loses no digits to cancellation.
+ *   x (n rows of d values, row stride ldx >= d): a strided view of the chain tensor goes in as it is.
+ *   logw (n) or NULL (all zero): log weights, normalised by the caller.
+ *   centre (d): the caller's common centre of the moments (the weighted mean of the sample).
+ *   mean (k x d); whiten: k matrices A_k (d x d, row-major) with Sigma_k^-1 = A_k A_k^T;
+ *   logc[k] = log pi_k + log|det A_k| - d/2 log 2 pi.
+ * Outputs, each may be NULL but not all three:
+ *   logpdf (n); resp (n rows of k values, row stride ldr >= k);
+ *   stats (k (1 + d + d d) + 2): with w_i = exp(logw[i]), N_j = sum_i w_i r_ij at [j], S1_j = sum_i w_i r_ij (x_i - c) at
+ *   [k + j d ..], S2_j = sum_i w_i r_ij (x_i - c)(x_i - c)^T at [k (1 + d) + j d d ..] (j the component), then sum_i w_i logpdf[i]
+ *   and sum_i w_i.  S2_k is stored full and EXACTLY symmetric: the upper tiles are computed and mirrored.
+ *   work: bfhip_gmm_work_bytes(n, d, k) bytes of the caller's, 256-byte aligned (0: arguments that bfhip_gmm_step refuses): 8 n k
+ *   bytes (t_ik, then w_i r_ik in its place), 16 bytes per 64 rows, and the partial statistics of at most 128 parts of rows.
+ * logpdf and resp do not look at logw; a row with a non-finite value has a NaN logpdf and NaN responsibilities.  In stats a row of
+ * weight -inf is no part of the sample, whatever it holds, NaN included; a NaN or +inf weight, or a non-finite row of weight above
+ * -inf, makes every entry of stats NaN.  The rows are cut into parts by n alone and every sum of stats has an order fixed by
+ * (n, d, k): the waves are folded first, then the parts, in increasing order, without atomics, so stats is bitwise repeatable; a row's
+ * logpdf and resp depend on that row and the parameters only -- the same bits alone, in any batch, at any offset.  Stream-ordered,
+ * no host synchronisation.
+ * BFHIP_ERR_ARG: n, d or k < 1, a null input, ldx < d, ldr < k, all three outputs NULL, a small or misaligned work buffer.
+ * BFHIP_ERR_UNSUPPORTED: d > BFHIP_MAX_DIM; k > BFHIP_GMM_MAX_K; n > 2^31 - 1. */
+#define BFHIP_GMM_MAX_K 32
+size_t bfhip_gmm_work_bytes(long n, int d, int k);
+int bfhip_gmm_step(bfhip_ctx *ctx, int d, int k, long n, const double *x, long ldx, const double *logw, const double *centre,
+                   const double *mean, const double *whiten, const double *logc, double *stats, double *logpdf, double *resp, long ldr,
+                   void *work, size_t work_bytes);
 
 /* The normal quantile function of n probabilities, out[i] = ndtri(p[i]) (scipy.special.ndtri, which scipy.stats.norm.ppf evaluates:
  * utils/sobol.py:57 on the Sobol points of multivariate_normal, transforms/sit.py:225 on the KDE cdfs): Cephes' algorithm; -inf / +inf
