@@ -104,6 +104,9 @@ SYMBOLS = {
     'bfhip_lstsq': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp]),
     'bfhip_lstsq_loo': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                   C.c_size_t]),
+    'bfhip_ridge_path': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_long,
+                                   _vp, _vp, _vp, _vp, _vp, C.c_size_t]),
+    'bfhip_ridge_rotate': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int]),
     'bfhip_sort_keys': (C.c_int, [_vp, C.c_long, _vp, _vp, _vp]),
     'bfhip_order_keys': (C.c_int, [_vp, C.c_long, _vp, _vp]),
     'bfhip_count_keys': (C.c_int, [_vp, C.c_long, _vp, C.c_long, _vp, C.c_int, _vp]),
@@ -184,6 +187,14 @@ MARG_MAX_BINS, MARG_MAX_BINS2D, MARG_MAX_LD = 1024, 128, 256   # BFHIP_MARG_MAX_
 MARG_EXTENT_WORK = 32768   # BFHIP_MARG_EXTENT_WORK: doubles of bfhip_marg_extent's work buffer
 LOO_TILE, LOO_WS_MAX, LOO_NSUM = 64, 1 << 28, 8   # BFHIP_LOO_TILE / _WS_MAX (doubles) / _NSUM
 LOO_SSE, LOO_PRESS, LOO_MAX, LOO_ARGMAX, LOO_SY, LOO_SYY, LOO_NUNIT = range(7)   # BFHIP_LOO_*: the columns of bfhip_lstsq_loo's sums
+RIDGE_MAX_L, RIDGE_TILE = 32, 64   # BFHIP_RIDGE_MAX_L / _TILE
+
+
+def ridge_work(n, r, m, L):
+    """BFHIP_RIDGE_WORK(n, r, m, L): doubles of bfhip_ridge_path's work buffer"""
+    return int(r) * RIDGE_MAX_L + (int(n) + RIDGE_TILE - 1) // RIDGE_TILE * int(L) * int(m) * 7
+
+
 PLOO_ELL, PLOO_Z, PLOO_NOUT = 0, 1, 16   # BFHIP_PLOO_ELL / _Z / _NOUT
 PLOO_ROWS = ('lpd', 'swe', 'waic', 'elpd_loo', 'khat', 'sigma', 'n_tail', 'cut', 'ess_loo', 'pit', 'max_r', 'flags', 'sw2', 'max_b')   # BFHIP_PLOO_LPD ...
 RW_ROWS = ('log_evidence_ratio', 'khat', 'sigma', 'n_tail', 'ess', 'flags', 'cut')   # BFHIP_RW_LER ...

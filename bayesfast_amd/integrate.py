@@ -80,6 +80,19 @@ def reference_classes(bayesfast=None):
         # the leave-one-out validation of the fit (a ``FitReport``) in ``fit_report``
         loo_on_fit = False
         fit_report = None
+        # True or a sequence of penalties: ``fit`` takes the ridge route of ``bayesfast_amd.PolyModel.fit_ridge`` (fewer points than
+        # parameters are then a legal fit) and leaves its ``RidgeReport`` in ``fit_report``
+        ridge_on_fit = False
+
+        def fit_ridge(self, x, y, logp=None, w=None, ridge=None):
+            """``fit`` by the ridge path of ``bayesfast_amd.PolyModel.fit_ridge``; returns its ``RidgeReport``."""
+            on = self.ridge_on_fit
+            self.ridge_on_fit = True if ridge is None else ridge
+            try:
+                self.fit(x, y, logp, w)
+            finally:
+                self.ridge_on_fit = on
+            return self.fit_report
 
         def fit_loo(self, x, y, logp=None, w=None):
             """``fit`` with the leave-one-out ``FitReport`` of ``bayesfast_amd.PolyModel.fit_loo``."""
@@ -96,6 +109,12 @@ def reference_classes(bayesfast=None):
             checks are those of ``bayesfast_amd.PolyModel.fit`` (same conditions and messages as :509-526)."""
             mirror = self._device_mirror()
             mirror.loo_on_fit = bool(self.loo_on_fit)
+            mirror.ridge_on_fit = self.ridge_on_fit
+            ridge = self.ridge_on_fit is not False and self.ridge_on_fit is not None
+            if ridge and self._use_bound and not self._all_linear and np.ndim(x) == 2 and np.shape(x)[0] <= self._input_size:
+                # (the ridge route takes fewer points than parameters, ``_set_bound`` below inverts the covariance of x: refuse
+                # before the coefficients are replaced, as ``bayesfast_amd.PolyModel.fit_ridge`` does)
+                raise ValueError('I need at least {} points, but you only gave me {}.'.format(self._input_size + 1, np.shape(x)[0]))
             _device_fit(mirror, x, y, logp, w)
             self.fit_report = mirror.fit_report
             for mine, fitted in zip(self.configs, mirror.configs):

@@ -1,4 +1,4 @@
 from .poly import PolyConfig, PolyModel
-from .fit_report import FitReport
+from .fit_report import FitReport, RidgeReport
 
-__all__ = ['PolyConfig', 'PolyModel', 'FitReport']
+__all__ = ['PolyConfig', 'PolyModel', 'FitReport', 'RidgeReport']

@@ -25,6 +25,9 @@ __all__ = ['PolyConfig', 'PolyModel']
 # doubles of workspace one ``fit_loo`` group may take for the leverage kernel's tiles in flight (BFHIP_LOO_WS_MAX: more is not
 # used); at least one tile's slice is always given.  A smaller value only means more passes: the numbers do not change.
 LOO_WORKSPACE_DOUBLES = _lib.LOO_WS_MAX
+# doubles of workspace one ``fit_ridge`` group may take for the rows of the design rotated into the eigenbasis; at least one tile of
+# BFHIP_RIDGE_TILE rows is always given.  A smaller value only means more passes over the rows: the numbers do not change.
+RIDGE_WORKSPACE_DOUBLES = _lib.LOO_WS_MAX
 
 BoundOptions = namedtuple('BoundOptions', ('use_bound', 'alpha', 'alpha_p', 'center_max'))
 _ORDERS = ('linear', 'quadratic', 'cubic-2', 'cubic-3')
@@ -300,7 +303,65 @@ class PolyModel(Surrogate):
         """Fit the polynomial model (modules/poly.py:505-589) on device.
 
         x (n, input_size), y (n, output_size); logp (n,) is only used for ``center_max``; w (n,) row weights."""
-        self.fit_report = self._fit(x, y, logp, w, bool(self.loo_on_fit))
+        on = self.ridge_on_fit
+        if on is not False and on is not None:
+            self._fit_ridge(x, y, logp, w, None if on is True else on)
+        else:
+            self.fit_report = self._fit(x, y, logp, w, bool(self.loo_on_fit))
+
+    # True or a sequence of penalties rho: ``fit()`` runs the ``fit_ridge`` route (and, like it, takes fewer points than parameters)
+    # and leaves its ``RidgeReport`` in ``fit_report``
+    ridge_on_fit = False
+
+    def fit_ridge(self, x, y, logp=None, w=None, ridge=None):
+        """A ridge-penalised fit with the penalty chosen by exact leave-one-out over a path of penalties, at no call of the true
+        model: what to do when ``fit_loo`` shows that a fit does not predict (q2 far below r2), or when there are fewer points than
+        parameters (n < n_param is a legal fit here; n >= 3).
+
+        ridge : 1 to 32 positive values of the dimensionless penalty rho, or None for 15 half-decades from 1e-6.  The fit minimises
+        |w (y - f)|^2 + n rho sum_j D_j c_j^2 with D_j the mean square of the (weighted) design column j; the constant is not
+        penalised.  Outputs that share a design share one path and one chosen rho.  Returns a ``RidgeReport``
+        (modules/fit_report.py; modules/ridge.py has the arithmetic), also left in ``fit_report``."""
+        return self._fit_ridge(x, y, logp, w, ridge)
+
+    def _fit_ridge(self, x, y, logp, w, ridge):
+        import torch
+        from ..device import get_context
+        from .fit_report import RidgeReport
+        from .ridge import check_ridge, ridge_group_device
+        ridge = check_ridge(ridge)
+        use_bound = self._use_bound and not self._all_linear
+        # (the bound's statistics invert the covariance of x: more points than inputs)
+        x, y, w = self._check_fit_args(x, y, w, max(3, self._input_size + 1 if use_bound else 0),
+                                       'I need at least {} points, but you only gave me {}.')
+        ctx = get_context()
+        n = x.shape[0]
+        xt = ctx.tensor(x, torch.float64)
+        wt = None if w is None else ctx.tensor(w, torch.float64)
+        bound = self._bound_stats(x, logp) if use_bound else None
+        entries, n_param = [], []
+        group_of_output = np.zeros(self._output_size, dtype=int)
+        for gi, (key, outs) in enumerate(self._design_groups().items()):
+            group_of_output[outs] = gi
+            confs, widths, P, A = self._design(ctx, key, xt, wt)
+            B = ctx.tensor(y[:, outs], torch.float64)
+            if wt is not None:
+                B = (B * wt[:, None]).contiguous()
+            # the constant: the first column of the group's linear config (csrc/bfhip_fit.hip: bf_design_block_kernel)
+            u_col = None
+            for c, col in zip(confs, np.cumsum([0] + widths[:-1])):
+                if c.order == 'linear':
+                    u_col = int(col)
+            entry, sol = ridge_group_device(ctx, A, B, wt, u_col, ridge, RIDGE_WORKSPACE_DOUBLES)
+            entry['outs'] = outs
+            self._scatter_solution(outs, confs, widths, sol)
+            entries.append(entry)
+            n_param.append(P)
+        self.fit_report = RidgeReport(n, n_param, group_of_output, entries, ridge)
+        self._touch()   # a refit: every device copy built before it is stale
+        if bound is not None:
+            self._apply_bound(*bound)
+        return self.fit_report
 
     def fit_loo(self, x, y, logp=None, w=None):
         """``fit``, and the leave-one-out validation of the fit it has made: a ``FitReport`` (modules/fit_report.py) with the
@@ -310,9 +371,8 @@ class PolyModel(Surrogate):
         self.fit_report = self._fit(x, y, logp, w, True)
         return self.fit_report
 
-    def _fit(self, x, y, logp, w, loo):
-        import torch
-        from ..device import get_context, _ptr
+    def _check_fit_args(self, x, y, w, n_min, what):
+        """x, y as arrays and w as a 1-d array or None, after the checks of modules/poly.py:509-526; at least n_min points."""
         x = np.asarray(x)
         y = np.asarray(y)
         if not (x.ndim == 2 and x.shape[-1] == self._input_size):
@@ -323,34 +383,64 @@ class PolyModel(Surrogate):
                              '{}.'.format(y.shape))
         if not x.shape[0] == y.shape[0]:
             raise ValueError('x and y have different # of points.')
-        if x.shape[0] < self.n_param:
-            raise ValueError('I need at least {} points, but you only gave me {}.'.format(self.n_param, x.shape[0]))
+        if x.shape[0] < n_min:
+            raise ValueError(what.format(n_min, x.shape[0]))
         if w is not None:
             w = np.atleast_1d(w)
             if not (w.ndim == 1 and w.shape[0] == x.shape[0]):
                 raise ValueError('invalid shape for w.')
+        return x, y, w
+
+    def _design_groups(self):
+        """Outputs that use the same set of configs share one design matrix: {recipe row: its outputs}, in order of appearance."""
+        groups = {}
+        for ii in range(self._output_size):
+            groups.setdefault(tuple(int(v) for v in self._recipe[ii]), []).append(ii)
+        return groups
+
+    def _design(self, ctx, key, xt, wt):
+        """The configs of a design group, their widths and the (weighted) design matrix A (n, P) on the device."""
+        import torch
+        from ..device import _ptr
+        n = xt.shape[0]
+        confs = [self._configs[k] for k in key if k >= 0]
+        widths = [c._a_shape[0] for c in confs]
+        P = int(sum(widths))
+        A = ctx.empty((n, P))
+        col = 0
+        for c, wd in zip(confs, widths):
+            xin = xt[:, torch.as_tensor(np.array(c._input_mask), device=ctx.device)].contiguous()
+            _lib.check(ctx._lib.bfhip_design_block(ctx.handle, _ORDERS.index(c.order), n, c.input_size, _ptr(xin), _ptr(wt), _ptr(A), P,
+                                                   col))
+            col += wd
+        return confs, widths, P, A
+
+    @staticmethod
+    def _scatter_solution(outs, confs, widths, sol):
+        """The packed solution sol (P, len(outs)) of a design group into its configs' coefficient blocks."""
+        for jo, ii in enumerate(outs):
+            k = 0
+            for c, wd in zip(confs, widths):
+                qq = int(np.argwhere(c._output_mask == ii)[0, 0])
+                c._set(sol[k:k + wd, jo], qq)
+                k += wd
+
+    def _fit(self, x, y, logp, w, loo):
+        import torch
+        from ..device import get_context, _ptr
+        x, y, w = self._check_fit_args(x, y, w, self.n_param, 'I need at least {} points, but you only gave me {}.')
         ctx = get_context()
         lib, h = ctx._lib, ctx.handle
         n = x.shape[0]
         xt = ctx.tensor(x, torch.float64)
         wt = None if w is None else ctx.tensor(w, torch.float64)
         # outputs that use the same set of configs share one design matrix and ONE factorisation
-        groups = {}
-        for ii in range(self._output_size):
-            groups.setdefault(tuple(int(v) for v in self._recipe[ii]), []).append(ii)
+        groups = self._design_groups()
         pending = []
         group_of_output = np.zeros(self._output_size, dtype=int)
         for gi, (key, outs) in enumerate(groups.items()):
             group_of_output[outs] = gi
-            confs = [self._configs[k] for k in key if k >= 0]
-            widths = [c._a_shape[0] for c in confs]
-            P = int(sum(widths))
-            A = ctx.empty((n, P))
-            col = 0
-            for c, wd in zip(confs, widths):
-                xin = xt[:, torch.as_tensor(np.array(c._input_mask), device=ctx.device)].contiguous()
-                _lib.check(lib.bfhip_design_block(h, _ORDERS.index(c.order), n, c.input_size, _ptr(xin), _ptr(wt), _ptr(A), P, col))
-                col += wd
+            confs, widths, P, A = self._design(ctx, key, xt, wt)
             B = ctx.tensor(y[:, outs], torch.float64)
             if wt is not None:
                 B = (B * wt[:, None]).contiguous()  # b *= w, modules/poly.py:567
@@ -423,13 +513,7 @@ class PolyModel(Surrogate):
                 torch.cuda.current_stream(ctx.device).wait_stream(ctx.stream)
                 S = work[:n * len(outs)].view(n, len(outs))   # B - A c at the returned coefficients
                 val['resid'] = S.clone() if wt is None else S / wt[:, None]
-            sol = r.cpu().numpy()
-            for jo, ii in enumerate(outs):
-                k = 0
-                for c, wd in zip(confs, widths):
-                    qq = int(np.argwhere(c._output_mask == ii)[0, 0])
-                    c._set(sol[k:k + wd, jo], qq)
-                    k += wd
+            self._scatter_solution(outs, confs, widths, r.cpu().numpy())
         report = None
         if loo:
             from .fit_report import FitReport

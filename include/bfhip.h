@@ -37,7 +37,9 @@ typedef struct bfhip_ctx bfhip_ctx;
 #define BFHIP_MAX_DIM 128         /* input_size limit of the device path */
 #define BFHIP_MAX_TREEDEPTH 12
 
-/* 116: bfhip_gmm_step (and bfhip_gmm_work_bytes), one EM iteration's pass over the draws for a Gaussian mixture: log density,
+/* bfhip_ridge_path and bfhip_ridge_rotate, the ridge path of the surrogate fit scored by exact leave-one-out for up to 32 penalties in
+ * one pass over the rotated design (additions only: the number stays).
+ * 116: bfhip_gmm_step (and bfhip_gmm_work_bytes), one EM iteration's pass over the draws for a Gaussian mixture: log density,
  * responsibilities and the weighted moments of every component (additions only).
  * 115: bfhip_health_chains, the per-chain sampler health figures (divergences, tree-depth limit, E-BFMI, depth histogram) read off the
  * statistics table in place (additions only).
@@ -445,6 +447,35 @@ int bfhip_lstsq(bfhip_ctx *ctx, int n, int P, int m, const double *A, int lda, c
 int bfhip_lstsq_loo(bfhip_ctx *ctx, int n, int P, int m, const double *A, int lda, const double *B, double *G, double *c,
                     int n_refine, double *work, int *info, double *h, double *e_loo, double *sums, const double *w, double *ws,
                     size_t ws_doubles);
+
+/* The ridge path of the fit scored by exact leave-one-out (PolyModel.fit_ridge).  For a fixed penalty ridge regression is least
+ * squares on augmented data, so S_i / (1 - h_i(lam)) is still the residual of row i under a fit without it.  The caller brings ONE
+ * symmetric eigen-decomposition: eigenvalues Lam (r,) >= 0, the rows of the rotated design Z (n, ldz >= r) and T (r, m) = Z^T B';
+ * the call scores all L <= BFHIP_RIDGE_MAX_L penalties lambdas (L,) > 0 (device arrays, like every array here) in one pass over Z,
+ * on the FP64 matrix cores, the right operand T_jo g_jl made as it is used:
+ *   complement = 0:  h_il = h0_i + sum_j z_ij^2 g_jl,  S_iol = B'_io - sum_j z_ij T_jo g_jl,  g_jl = 1 / (Lam_j + lambda_l);
+ *   complement = 1 (more columns than rows; Z orthonormal columns that span what h0 leaves, Lam and T in that basis):
+ *                    1 - h_il = sum_j z_ij^2 g_jl,  S_iol = sum_j z_ij T_jo g_jl,  g_jl = lambda_l / (Lam_j + lambda_l), summed
+ *                    directly: nothing of the form 1 - (...) cancels.  Bp and h0 are not read.
+ * Bp (n, m) are the targets B' the fit sees, Bw (n, m) the weighted targets of the SY / SYY slots, h0 (n,) the leverage of the
+ * unpenalised part or NULL, w (n,) the row weights or NULL.
+ *   h (n, L)                      the leverages;
+ *   sums (L, m, BFHIP_LOO_NSUM)   per penalty and output, the slots of bfhip_lstsq_loo with the same definitions (e_loo =
+ *                                 S / ((1 - h) w); +-inf and a count in _NUNIT where 1 - h <= 0; _ARGMAX the first row of the maximum);
+ *   resid, e_loo (n, m)           S / w and e_loo, both in the units of B / w: given together or both NULL, and only for L = 1.
+ * row0: the rows are rows row0 .. row0 + n - 1 of a longer series taken in passes (a multiple of BFHIP_RIDGE_TILE): _ARGMAX counts
+ * from it and, when row0 > 0, the sums continue those already in `sums`, in the order one call over all rows has.  work holds
+ * BFHIP_RIDGE_WORK(n, r, m, L) doubles.  The order of every sum is fixed by (n, r, m, L): two calls give the same bits, and so do passes. */
+#define BFHIP_RIDGE_MAX_L 32
+#define BFHIP_RIDGE_TILE 64
+#define BFHIP_RIDGE_WORK(n, r, m, L) \
+    ((size_t)(r) * BFHIP_RIDGE_MAX_L + (size_t)(((n) + BFHIP_RIDGE_TILE - 1) / BFHIP_RIDGE_TILE) * (size_t)(L) * (size_t)(m) * 7)
+int bfhip_ridge_path(bfhip_ctx *ctx, int n, int r, int m, int L, const double *Z, int ldz, const double *Lam, const double *T,
+                     const double *lambdas, const double *Bp, const double *Bw, const double *h0, const double *w, int complement,
+                     long row0, double *h, double *sums, double *resid, double *e_loo, double *work, size_t work_doubles);
+/* Z (n, ldz >= r) = A (n, lda >= P) V (P, ldv >= r), row-major, on the FP64 matrix cores: the rows of a design in the eigenbasis.
+ * A row's sums run over the columns of A in order whatever n is, so rows rotated in passes have the bits of one call. */
+int bfhip_ridge_rotate(bfhip_ctx *ctx, int n, int P, int r, const double *A, int lda, const double *V, int ldv, double *Z, int ldz);
 
 /* ------------------------------------------------------------------------------------------------
  * Refit glue: the steps either side of the sampler inside Recipe._sam_step / _pos_step.
